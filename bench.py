@@ -2,7 +2,7 @@
 """Benchmark of the LM refinement hot path (BASELINE.json metric: LM iterations/s and
 point-residuals/s on a synthetic checkerboard dataset).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step = ONE LM iteration (src/calibrate.py:143-168) over the rank's resident views:
@@ -11,14 +11,19 @@ kernel; `--lm-mode two_kernel` materialises the compact J in HBM between a jacob
 kernel instead), per-view Schur elimination, (N > 1: one RCCL all-reduce of the reduce
 buffer), accept/reject + L x L solve, back-substitution. Termination tests are disabled for the timed region
 (lam_min = 0, lam_max = inf, err_min = -inf) so that exactly K iterations execute, each
-with full work. `value` is WEAK scaling (every rank holds `views` views of the config); at N > 1 the line also
-carries a `strong` block -- the config's GLOBAL problem (c3: 10 000 views, c5: 1 000 000) split N ways -- and, in
-`exchange`, the same K steps timed with every carrier of the per-round sum that passes its self-test (the library's
-own ncclAllReduce, torch.distributed.all_reduce; with `--allreduce all` also the in-kernel peer exchange); `value` is
-taken with RCCL.
+with full work. `value` is WEAK scaling (every rank holds `views` views of the config); `value` is taken with RCCL.
+
+A plain run sets up, warms up, times exactly K steps, writes the outputs of the last timed refinement
+(--dump-outputs) and prints the line. `--full` adds everything else the line can carry: the K-step segment repeated
+for --min-seconds with HIP events on the dominant kernel (`timing.repeated_segments`, the rooflines), the
+two-kernel pass, the Calibrator-level API end to end, the CPU baseline and, at N > 1, a `strong` block -- the
+config's GLOBAL problem (c3: 10 000 views, c5: 1 000 000) split N ways -- and, in `exchange`, the same K steps timed
+with every carrier of the per-round sum that passes its self-test (the library's own ncclAllReduce,
+torch.distributed.all_reduce; with `--allreduce all` also the in-kernel peer exchange).
 One JSON line is printed by rank 0.
 """
 import argparse
+import gc
 import json
 import os
 import sys
@@ -223,6 +228,32 @@ def apiEndToEnd(cca, synthetic, shard, cfg, workload, local, noise):
     return out
 
 
+DUMP_LIMIT_BYTES = 63 * 10 ** 6      # all --dump-outputs files together stay below 64 MB
+
+
+def dumpOutputs(directory, P, sse, trace):
+    """--dump-outputs: what lmEnd hands its caller for the last timed refinement -- the parameter vector, its sse and the
+    per-iteration trace -- as float64 DIR/<name>.npy. A parameter vector too large for the limit is written as a fixed,
+    seeded sample of its entries, the shared parameters always among them (P_sample_index.npy holds the positions).
+    Files an earlier dump left in DIR under any of these names are removed first, so DIR holds one run's outputs."""
+    os.makedirs(directory, exist_ok=True)
+    for name in ("P", "P_sample", "P_sample_index", "sse", "trace"):
+        path = os.path.join(directory, name + ".npy")
+        if os.path.exists(path):
+            os.remove(path)
+    P = np.asarray(P, dtype=np.float64)
+    arrays = {"sse": np.array([sse], dtype=np.float64), "trace": np.asarray(trace, dtype=np.float64)}
+    budget = DUMP_LIMIT_BYTES - sum(a.nbytes for a in arrays.values())
+    if P.nbytes <= budget:
+        arrays["P"] = P
+    else:
+        n = budget // 16 - 16                     # a value and its position per sampled entry
+        idx = np.unique(np.concatenate((np.arange(16), np.random.default_rng(0).choice(P.size, n, replace=False))))
+        arrays["P_sample"], arrays["P_sample_index"] = P[idx], idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def strongShardRange(totalViews, world, rank):
     """views [start, end) of `rank` when `totalViews` views of one global problem are split over `world` ranks"""
     from camera_calibration_amd import distributed
@@ -239,18 +270,25 @@ class Carrier:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100, help="LM iterations per timed segment (<= 100)")
+    ap.add_argument("--steps", type=int, default=100, help="LM iterations timed (as refinements of at most 100 each)")
     ap.add_argument("--min-seconds", type=float, default=2.0,
-                    help="the K-step segment is repeated until the timed phase lasts at least this long")
+                    help="--full: the K-step segment is repeated until this phase lasts at least this long")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside `value`: repeated segments with kernel timing and rooflines, "
+                         "the two-kernel pass, the API end to end, the CPU baseline, N > 1: strong scaling and every carrier")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write P, sse and the trace of the last timed refinement as DIR/<name>.npy (float64)")
     ap.add_argument("--workload", default="c3", help="c2 | c3 | c4 | c5 (BASELINE.json configs[1..4])")
     ap.add_argument("--views", type=int, default=None, help="views per GPU (default: the config's)")
     ap.add_argument("--noise", type=float, default=0.1, help="sensor noise sigma in px")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-api", action="store_true", help="skip the api_end_to_end block (Calibrator-level calls, N = 1 only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline block")
+    ap.add_argument("--no-api", action="store_true",
+                    help="--full: skip the api_end_to_end block (Calibrator-level calls, N = 1 only)")
     ap.add_argument("--scaling", choices=["both", "weak", "strong"], default="both",
                     help="N > 1: 'weak' = every rank holds the config's per-GPU views (this is `value`); 'strong' = the "
-                         "config's global problem split N ways (block `strong`); 'both' (default) measures the two")
+                         "config's global problem split N ways (block `strong`); 'both' (default) measures the two, the "
+                         "strong block with --full")
     ap.add_argument("--allreduce", choices=["auto", "all", "peer", "direct", "torch"], default="auto",
                     help="the one exchange per LM step at N > 1. 'direct': ncclAllReduce issued by the library on its own "
                          "stream; 'torch': torch.distributed.all_reduce on the bound buffer; 'peer': the reduce kernel itself "
@@ -316,9 +354,11 @@ def main():
     perGpuDefault = cfg["views"] // 8 if args.workload in ("c4", "c5") else cfg["views"]
     viewsPerGpu = args.views or perGpuDefault
     lmOpts = dict(lamInit=1e-3, lamMin=0.0, lamMax=float("inf"), errMin=-float("inf"))
+    # with the stop rule disabled lambda leaves the fp64 range after ~310 consecutive rejections at the noise floor, so
+    # one refinement runs at most SEG iterations and longer runs are several refinements from the same P0
     SEG = 100
-    if args.steps > SEG:
-        sys.exit(f"bench.py: --steps is at most {SEG} (lambda leaves the fp64 range in longer runs with the stop rule off)")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be at least 1 and --warmup at least 0")
     # HIP events around the dominant kernel's launches inside the timed region, on the stream they are launched on.
     # An event pair keeps a launch from being dispatched back to back with its neighbours (c3: +12 us per LM round when
     # every launch is bracketed), so every 16th launch is timed -- whatever --steps is.
@@ -337,9 +377,10 @@ def main():
         eng.setLmMode(args.lm_mode)
         return eng, tUp
 
-    def makeCarriers(shard, eng0, want):
-        """-> list of Carrier, the one `value` is taken with first. Every carrier is self-tested and agreed on by all
-        ranks before it is used; the first engine is reused by the first carrier that comes up."""
+    def makeCarriers(shard, eng0, want, firstOnly=False):
+        """-> list of Carrier, the one `value` is taken with first (with firstOnly, that one alone). Every carrier is
+        self-tested and agreed on by all ranks before it is used; the first engine is reused by the first carrier
+        that comes up."""
         out = []
         spare = [eng0]
 
@@ -355,11 +396,11 @@ def main():
                 spare.append(e)
                 if want == "direct":
                     sys.exit("bench.py --allreduce direct: the in-library all-reduce could not be set up")
-        if want in ("auto", "all", "torch"):
+        if want in ("auto", "all", "torch") and not (firstOnly and out):
             e = engine()
             out.append(Carrier("torch", e, distributed.ShardedLM(e, distributed.torchAllReduce(e, devTorch)),
                                "torch.distributed.all_reduce"))
-        if want in ("all", "peer") and world > 1:
+        if want in ("all", "peer") and world > 1 and not (firstOnly and out):
             e = engine()
             ar = distributed.peerExchange(e)
             if ar is not None:
@@ -377,17 +418,12 @@ def main():
             e.close()
         return out
 
-    def measure(shard, eng, lm, minSeconds, profile):
-        """R timed segments of exactly --steps LM iterations on `eng` (through `lm` when sharded).
-        A timed SEGMENT is exactly K = --steps LM iterations of one refinement: lmBegin (upload of P0, state reset)
-        and the bootstrap pass that evaluates P0 are issued and drained BEFORE the clock starts, lmEnd (download of
-        P and the trace) runs after it stops -- they are per-refinement costs, reported as segment_overhead_ms.
-        With the stop rule disabled lambda overflows after ~310 consecutive rejections at the noise floor, so a
-        segment holds at most SEG iterations and every segment restarts from the same perturbed P0 (lambda 1e-3,
-        src/calibrate.py:142). The segment is repeated R times (R agreed by all ranks from one calibration
-        segment, so that the timed phase lasts >= --min-seconds) and the MEDIAN segment is reported."""
-        state = {"P": shard["P0"], "iters": 0, "trace": [], "sse": float("nan")}
-
+    def segmentRunner(shard, eng, lm, state):
+        """-> segment(k, timed=True): one refinement of k <= SEG timed LM iterations on `eng` (through `lm` when
+        sharded), from the same perturbed P0 every time (lambda 1e-3, src/calibrate.py:142). lmBegin (upload of P0,
+        state reset) and the bootstrap pass that evaluates P0 are issued and drained BEFORE the clock starts, lmEnd
+        (download of P and the trace) runs after it stops -- they are per-refinement costs, reported as overhead.
+        lmEnd's results go to `state`; segment() returns (timed seconds, overhead seconds)."""
         def drain():
             eng.synchronize()             # the engine's own stream (a wait, no copy: lmDone's 1 KiB read-back cost ~10 us)
             torch.cuda.synchronize()
@@ -413,32 +449,77 @@ def main():
             t1 = time.perf_counter()
             sse_, P_, it_, tr_ = eng.lmEnd()
             t2 = time.perf_counter()
-            state["P"], state["sse"] = P_, sse_
+            state["P"], state["sse"], state["lastTrace"] = P_, sse_, tr_
             state["iters"] += it_
             state["trace"].append(tr_)
             return t1 - t0, (t0 - tb) + (t2 - t1)
+        return segment
 
-        # Everything slow is done before the warm-up, so that the device is not left idle between the warm-up
-        # and the timed region: after >= 20 ms of idleness the GPU's clocks have dropped and the next ~1 ms of
-        # work runs slow. So: event pool and collector first, then an untimed spin-up that brings the clocks up
-        # (setup, like generating the data), the W warm-up steps, then the timed segments back to back.
-        import gc
-        if profile:
-            eng.profileEnable(True, every=PROF_EVERY)         # creates the event pool (tens of ms, once)
-        gc.collect()
-        gc.disable()              # no collector pauses inside the timed region (ranks wait for the slowest each round)
+    def slowestRank(*arrays):
+        """element-wise max over the ranks of equally long float arrays (per segment: the slowest rank)"""
+        if dist is None:
+            return arrays
+        n = len(arrays[0])
+        tt = torch.from_numpy(np.concatenate(arrays)).to("cuda")
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        both = tt.cpu().numpy()
+        return tuple(both[i * n:(i + 1) * n] for i in range(len(arrays)))
+
+    def newState(shard):
+        return {"P": shard["P0"], "iters": 0, "trace": [], "sse": float("nan"), "lastTrace": None}
+
+    # Everything slow is done before the warm-up, so that the device is not left idle between the warm-up and the
+    # timed region: after >= 20 ms of idleness the GPU's clocks have dropped and the next ~1 ms of work runs slow.
+    # So: collector (and, in measure(), event pool) first, then an untimed spin-up that brings the clocks up (setup,
+    # like generating the data), the W warm-up steps, then the timed segments back to back.
+    def spinUp(segment):
         tSpin = time.perf_counter()
         for _ in range(3):
             segment(SEG, timed=False)                          # clock spin-up, ~25 ms of device work
-        tSpin = time.perf_counter() - tSpin
-        if args.warmup > 0:
-            segment(min(args.warmup, SEG), timed=False)
-        tCal, _ = segment(args.steps)                          # one calibration segment fixes the repeat count on every rank
-        if dist is not None:
-            tc = torch.tensor([tCal], dtype=torch.float64, device="cuda")
-            dist.all_reduce(tc, op=dist.ReduceOp.MAX)
-            tCal = float(tc.item())
-        R = int(min(2001, max(5, np.ceil(minSeconds / max(tCal, 1e-6)))))
+        return time.perf_counter() - tSpin
+
+    def refinements(k):
+        """k LM iterations as refinements of at most SEG iterations each"""
+        return [SEG] * (k // SEG) + ([k % SEG] if k % SEG else [])
+
+    def timeSteps(shard, eng, lm):
+        """`value`: exactly --steps timed LM iterations, as refinements of at most SEG iterations, after the spin-up and
+        exactly --warmup untimed iterations. elapsed = the sum of the refinements' timed parts."""
+        state = newState(shard)
+        segment = segmentRunner(shard, eng, lm, state)
+        gc.collect()
+        gc.disable()              # no collector pauses inside the timed region (ranks wait for the slowest each round)
+        tSpin = spinUp(segment)
+        for k in refinements(args.warmup):
+            segment(k, timed=False)
+        state["iters"], state["trace"] = 0, []
+        ks = refinements(args.steps)
+        segTimes, segOver = np.zeros(len(ks)), np.zeros(len(ks))
+        for j, k in enumerate(ks):
+            segTimes[j], segOver[j] = segment(k)
+        gc.enable()
+        segTimes, segOver = slowestRank(segTimes, segOver)
+        return {"elapsed": float(segTimes.sum()), "refinements": len(ks), "segOver": segOver, "tSpin": tSpin,
+                "iters": state["iters"], "total": args.steps, "sse": state["sse"], "P": state["P"],
+                "trace": np.vstack(state["trace"]), "lastTrace": state["lastTrace"]}
+
+    def measure(shard, eng, lm, minSeconds, profile):
+        """--full: R timed segments of exactly min(--steps, SEG) LM iterations each on `eng` (through `lm` when sharded),
+        R agreed by all ranks from one calibration segment so that the timed phase lasts >= --min-seconds; the MEDIAN
+        segment is reported. With `profile` every PROF_EVERY-th launch of the dominant kernels is timed by HIP events."""
+        state = newState(shard)
+        segment = segmentRunner(shard, eng, lm, state)
+        k = min(args.steps, SEG)
+        if profile:
+            eng.profileEnable(True, every=PROF_EVERY)         # creates the event pool (tens of ms, once)
+        gc.collect()
+        gc.disable()
+        tSpin = spinUp(segment)
+        for w in refinements(args.warmup):
+            segment(w, timed=False)
+        tCal, _ = segment(k)                                   # one calibration segment fixes the repeat count on every rank
+        (tCal,) = slowestRank(np.array([tCal]))
+        R = int(min(2001, max(5, np.ceil(minSeconds / max(float(tCal[0]), 1e-6)))))
         R += 1 - R % 2                                         # odd: the median is one of the segments
         itersBefore = state["iters"]
         state["trace"] = []
@@ -447,16 +528,13 @@ def main():
         segTimes, segOver = np.zeros(R), np.zeros(R)
         tPhase = time.perf_counter()
         for j in range(R):
-            segTimes[j], segOver[j] = segment(args.steps)
+            segTimes[j], segOver[j] = segment(k)
         tPhase = time.perf_counter() - tPhase
         gc.enable()
-        if dist is not None:                                   # per segment: the slowest rank
-            tt = torch.from_numpy(np.concatenate((segTimes, segOver))).to("cuda")
-            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-            both = tt.cpu().numpy()
-            segTimes, segOver = both[:R], both[R:]
-        res = {"elapsed": float(np.median(segTimes)), "R": R, "segTimes": segTimes, "segOver": segOver, "tPhase": tPhase,
-               "tSpin": tSpin, "iters": state["iters"] - itersBefore, "total": args.steps * R, "sse": state["sse"], "P": state["P"],
+        segTimes, segOver = slowestRank(segTimes, segOver)
+        res = {"elapsed": float(np.median(segTimes)), "stepsPerSegment": k, "R": R, "segTimes": segTimes,
+               "segOver": segOver, "tPhase": tPhase, "tSpin": tSpin, "iters": state["iters"] - itersBefore,
+               "total": k * R, "sse": state["sse"], "P": state["P"],
                "trace": np.vstack(state["trace"]) if state["trace"] else np.zeros((0, 5 + eng.L))}
         if profile:
             res["prof"] = [eng.profileRead(i) for i in range(3)]
@@ -485,39 +563,49 @@ def main():
     ranksSeen = 1
     carriers = []
     if dist is not None:
-        carriers = makeCarriers(shard, eng, args.allreduce)
+        carriers = makeCarriers(shard, eng, args.allreduce, firstOnly=not args.full)
         # how many ranks the process group really has (not WORLD_SIZE): every rank contributes a one
         seen = torch.ones(1, dtype=torch.int32, device=devTorch if args.backend == "nccl" else "cpu")
         dist.all_reduce(seen)
         ranksSeen = int(seen.item())
         eng = carriers[0].eng
     main = carriers[0] if carriers else None
-    exchange = {}
-    m = measure(shard, eng, main.lm if main else None, args.min_seconds, profile=True)
-    if main:
-        exchange[main.name] = m["elapsed"] / args.steps * 1e3
-    for c in carriers[1:]:                                     # the same K steps with the other carriers
-        mc = measure(shard, c.eng, c.lm, min(args.min_seconds, 0.25), profile=False)
-        exchange[c.name] = mc["elapsed"] / args.steps * 1e3
+    m = timeSteps(shard, eng, main.lm if main else None)
+    elapsed, sse, P, iters, total, trace = m["elapsed"], m["sse"], m["P"], m["iters"], m["total"], m["trace"]
     MNglobal = globalPoints(MNlocal)
+    if args.dump_outputs and rank == 0:
+        dumpOutputs(args.dump_outputs, P, sse, m["lastTrace"])
+
+    full = exchange = strong = tUpload2 = twoKernelMsPerStep = None
+    prof = [(0.0, 0)] * 3
+    jacSteps = gramSteps = min(args.steps, SEG)
+    if args.full:
+        # the K-step segment repeated for --min-seconds with HIP events on the dominant kernels (the rooflines)
+        full = measure(shard, eng, main.lm if main else None, args.min_seconds, profile=True)
+        prof = full["prof"]
+        if main:
+            exchange = {main.name: full["elapsed"] / full["stepsPerSegment"] * 1e3}
+        for c in carriers[1:]:                                 # the same K steps with the other carriers
+            mc = measure(shard, c.eng, c.lm, min(args.min_seconds, 0.25), profile=False)
+            exchange[c.name] = mc["elapsed"] / mc["stepsPerSegment"] * 1e3
 
     # ------------------------------------------------------------------ strong block: the config's global problem / N
-    strong = None
-    if dist is not None and args.scaling == "both":
+    if args.full and dist is not None and args.scaling == "both":
         totalViews = cfg["views"] if args.views is None else args.views * world
         v0, v1 = strongShardRange(totalViews, world, rank)
         if v1 - v0 == viewsPerGpu and world * viewsPerGpu == totalViews:
             # the weak shard IS the strong shard (c4 / c5 at N = 8): measured once
-            strong = {"note": "identical to the weak block at this N", "value": MNglobal * args.steps / m["elapsed"],
-                      "ms_per_step": m["elapsed"] / args.steps * 1e3, "global_views": totalViews, "views_per_gpu": v1 - v0}
+            strong = {"note": "identical to the weak block at this N", "value": MNglobal * args.steps / elapsed,
+                      "ms_per_step": elapsed / args.steps * 1e3, "global_views": totalViews, "views_per_gpu": v1 - v0}
         else:
             sshard = synthetic.makeShard(cfg, viewStart=v0, numViews=v1 - v0, noiseSigma=args.noise, device=local)
             seng, _ = makeEngine(sshard)
             scar = makeCarriers(sshard, seng, {"rccl_direct": "direct", "torch": "torch", "peer": "peer"}[main.name])
             ms = measure(sshard, scar[0].eng, scar[0].lm, min(args.min_seconds, 0.3), profile=False)
             sglobal = globalPoints(int(sshard["viewOffsets"][-1]))
-            strong = {"value": sglobal * args.steps / ms["elapsed"], "unit": "point-residuals/s",
-                      "lm_iters_per_s": args.steps / ms["elapsed"], "ms_per_step": ms["elapsed"] / args.steps * 1e3,
+            k = ms["stepsPerSegment"]
+            strong = {"value": sglobal * k / ms["elapsed"], "unit": "point-residuals/s",
+                      "lm_iters_per_s": k / ms["elapsed"], "ms_per_step": ms["elapsed"] / k * 1e3,
                       "global_views": totalViews, "views_per_gpu": v1 - v0, "global_points": sglobal,
                       "allreduce": scar[0].name, "segments": int(ms["R"]), "valid": bool(ms["iters"] == ms["total"]),
                       "what": f"the config's global problem ({totalViews} views) split over {world} ranks, views [{v0}, {v1}) "
@@ -526,17 +614,13 @@ def main():
                 c.eng.close()
         strong["scaling"] = "strong"
 
-    # the same upload once more: what a caller pays per calib_set_problem once the handle's pinned staging exists
-    # (the first call above also pays for pinning 8 MiB and the first use of the packing kernel)
-    t0 = time.perf_counter()
-    eng.setProblem(shard["viewOffsets"], shard["sensorPoints"], shard["modelPoints"])
-    tUpload2 = time.perf_counter() - t0
-    elapsed, R, segTimes, segOver = m["elapsed"], m["R"], m["segTimes"], m["segOver"]
-    sse, P, iters, total, trace = m["sse"], m["P"], m["iters"], m["total"], m["trace"]
-    (jacMs, jacN), (gramMs, gramN), (fusedMs, fusedN) = m.get("prof", [(0.0, 0)] * 3)
-    twoKernelMsPerStep = None
-    jacSteps = gramSteps = args.steps
-    if rank == 0 and args.lm_mode == "fused":
+    if args.full:
+        # the same upload once more: what a caller pays per calib_set_problem once the handle's pinned staging exists
+        # (the first call above also pays for pinning 8 MiB and the first use of the packing kernel)
+        t0 = time.perf_counter()
+        eng.setProblem(shard["viewOffsets"], shard["sensorPoints"], shard["modelPoints"])
+        tUpload2 = time.perf_counter() - t0
+    if args.full and rank == 0 and args.lm_mode == "fused":
         # the same shard through the two-kernel path (compact J through HBM), timed for the
         # HBM roofline of the jacobian kernel and the gram kernel; not part of `value`, and not
         # allowed to take the bench line down with it
@@ -552,13 +636,13 @@ def main():
             eng2.lmRun(10)
             eng2.lmDone()
             twoKernelMsPerStep = (time.perf_counter() - t2) / 10 * 1e3
-            jacMs, jacN = eng2.profileRead(0)
-            gramMs, gramN = eng2.profileRead(1)
+            prof = [eng2.profileRead(0), eng2.profileRead(1), prof[2]]
             jacSteps = gramSteps = 10
             eng2.lmEnd()
             eng2.close()
         except Exception as e:
             print(f"bench: two-kernel pass skipped: {e}", file=sys.stderr)
+    (jacMs, jacN), (gramMs, gramN), (fusedMs, fusedN) = prof
 
     if rank == 0:
         L = eng.L
@@ -643,16 +727,11 @@ def main():
             "lm_iters_per_s": args.steps / elapsed,
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3,
-            "timing": {"what": "median over `segments` timed segments of exactly `steps` LM iterations each (max over "
-                               "ranks per segment); lmBegin, the bootstrap pass and lmEnd are outside the segments "
-                               "(round 1 timed ONE region, a mean that included them: `ms_per_step_whole_refinement` is "
-                               "that definition)",
-                       "segments": int(R), "segment_ms_min": float(segTimes.min() * 1e3),
-                       "segment_ms_median": float(np.median(segTimes) * 1e3), "segment_ms_max": float(segTimes.max() * 1e3),
-                       "segment_overhead_ms": float(np.median(segOver) * 1e3),
-                       "ms_per_step_whole_refinement": float(np.mean(segTimes + segOver) / args.steps * 1e3),
-                       "ms_per_refinement": float(np.mean(segTimes + segOver) * 1e3),
-                       "timed_phase_s": float(m["tPhase"])},
+            "timing": {"what": "exactly `steps` LM iterations, as `refinements` of at most 100 iterations each from the same "
+                               "P0 (max over ranks per refinement); lmBegin, the bootstrap pass and lmEnd are outside the "
+                               "timed region",
+                       "refinements": m["refinements"], "timed_region_s": elapsed,
+                       "refinement_overhead_ms": float(np.median(m["segOver"]) * 1e3)},
             "higher_is_better": True, "scaling": "strong" if strongOnly else "weak", "vs_baseline": None,
             "dtype": cfg["dtype"], "data": "synthetic",
             "config": {"workload": f"{args.workload}: {viewsPerGpu} views x {shard['pointsPerView']} pts per GPU, "
@@ -666,9 +745,37 @@ def main():
                                                                         else "exact sums of rank-dependent values over all ranks, against a deadline, passed on every rank"),
                        "lm_mode": args.lm_mode,
                        "fused_form": dict(zip(("share", "waves"), eng.fusedForm()))},
-            "exchange": None if dist is None else {"ms_per_step": exchange, "what": "the same K steps of the weak block with every "
-                                                   "carrier of the per-round sum that passed its self-test on every rank "
-                                                   "(the peer exchange only with --allreduce all | peer)",
+            "valid": bool(iters == total),
+            "lm": {"accepted_steps_in_timed_region": accepted, "final_sse": sse,
+                   "iterations_executed": int(iters), "iterations_requested": int(total),
+                   "note": "sensor noise makes the estimate differ from the generating parameters (statistical "
+                           "error); parity with the reference is asserted on noise-free data in tests/",
+                   "max_rel_err_intrinsics_vs_truth": float(np.max(np.abs(P[:L] - shard["Ptrue"][:L])
+                                                                   / np.maximum(np.abs(shard["Ptrue"][:L]), 1.0)))},
+            "setup_s": {"generate": tGen, "pack_upload": tUpload, "clock_spinup_300_untimed_iterations": m["tSpin"]},
+        }
+        if iters != total:
+            # with the stop rule disabled lambda still overflows to inf after ~310 consecutive rejections
+            # (x10 each): the loop then ends early and later rounds are no-ops -- such a run is not a measurement
+            print(f"bench: only {iters} of {total} LM iterations executed (lambda left the fp64 range)", file=sys.stderr)
+    if rank == 0 and args.full:
+        segTimes, segOver, k = full["segTimes"], full["segOver"], full["stepsPerSegment"]
+        out["timing"]["repeated_segments"] = {
+            "what": "median over `segments` timed segments of exactly min(`steps`, 100) LM iterations each (max over "
+                    "ranks per segment), HIP events on every `roofline.timed_every_nth_launch`-th launch of the "
+                    "dominant kernel; `ms_per_step_whole_refinement` includes lmBegin, the bootstrap pass and lmEnd",
+            "steps_per_segment": k, "ms_per_step": full["elapsed"] / k * 1e3,
+            "segments": int(full["R"]), "segment_ms_min": float(segTimes.min() * 1e3),
+            "segment_ms_median": float(np.median(segTimes) * 1e3), "segment_ms_max": float(segTimes.max() * 1e3),
+            "segment_overhead_ms": float(np.median(segOver) * 1e3),
+            "ms_per_step_whole_refinement": float(np.mean(segTimes + segOver) / k * 1e3),
+            "ms_per_refinement": float(np.mean(segTimes + segOver) * 1e3),
+            "timed_phase_s": float(full["tPhase"]), "valid": bool(full["iters"] == full["total"])}
+        out.update({
+            "exchange": None if dist is None else {"ms_per_step": exchange, "what": "the K-step segments of the weak block "
+                                                   "(timing.repeated_segments) with every carrier of the per-round sum that "
+                                                   "passed its self-test on every rank (the peer exchange only with "
+                                                   "--allreduce all | peer)",
                                                    "backend": args.backend},
             "strong": strong,
             "roofline": mainRoof,
@@ -684,23 +791,9 @@ def main():
                                                "`roofline.frac` of the matrix peak; this kernel re-reads a materialised J and is bound by "
                                                "the memory system (4 flop/B), which is what its low MFMA utilisation says",
                               "points_per_launch": gramPts, "launches_per_step": gramN / gramSteps,
-                              "avg_launch_ms": gramAvgMs, "launches_timed": gramN},
-            "valid": bool(iters == total),
-            "lm": {"accepted_steps_in_timed_region": accepted, "final_sse": sse,
-                   "iterations_executed": int(iters), "iterations_requested": int(total),
-                   "note": "sensor noise makes the estimate differ from the generating parameters (statistical "
-                           "error); parity with the reference is asserted on noise-free data in tests/",
-                   "max_rel_err_intrinsics_vs_truth": float(np.max(np.abs(P[:L] - shard["Ptrue"][:L])
-                                                                   / np.maximum(np.abs(shard["Ptrue"][:L]), 1.0)))},
-            "setup_s": {"generate": tGen, "pack_upload": tUpload, "pack_upload_second_call": tUpload2,
-                        "pack_upload_second_call_GBps": (MNlocal * 40 / tUpload2 / 1e9) if tUpload2 > 0 else None,
-                        "clock_spinup_300_untimed_iterations": m["tSpin"]},
-        }
-        if iters != total:
-            # with the stop rule disabled lambda still overflows to inf after ~310 consecutive rejections
-            # (x10 each): the loop then ends early and later rounds are no-ops -- such a run is not a measurement
-            print(f"bench: only {iters} of {total} LM iterations executed (lambda left the fp64 range); "
-                  f"use fewer --steps", file=sys.stderr)
+                              "avg_launch_ms": gramAvgMs, "launches_timed": gramN}})
+        out["setup_s"].update({"pack_upload_second_call": tUpload2,
+                               "pack_upload_second_call_GBps": (MNlocal * 40 / tUpload2 / 1e9) if tUpload2 > 0 else None})
         if world == 1 and not args.no_api and args.lm_mode == "fused":
             try:
                 out["api_end_to_end"] = apiEndToEnd(cca, synthetic, shard, cfg, args.workload, local, args.noise)
@@ -717,6 +810,7 @@ def main():
                                                    "the N = 1 line")
             except Exception as e:
                 out["cpu_baseline"] = {"error": str(e)}
+    if rank == 0:
         sys.stdout.flush()
         os.dup2(stdoutFd, 1)
         print(json.dumps(out), flush=True)

@@ -7,8 +7,10 @@ widths: the wave cuts fall anywhere in the views, batches straddle view boundari
 usage: python tools/fuzz_forms.py [trials] [seed]"""
 import itertools
 import os
+import shutil
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
@@ -34,6 +36,8 @@ def main():
     from oracle import c_oracle, calib_oracle as orc
     trials = int(sys.argv[1]) if len(sys.argv) > 1 else 12
     rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
+    tmp = tempfile.mkdtemp(prefix="fuzz_forms_")        # per run: another run or user may own fixed names in /tmp
+    fin, fout = os.path.join(tmp, "fuzz_in.npz"), os.path.join(tmp, "fuzz_out.npz")
     worst = 0.0
     for t in range(trials):
         name = ["radtan", "fisheye"][t % 2]
@@ -52,24 +56,24 @@ def main():
         pts = np.column_stack((rng.uniform(0, 0.48, MN), rng.uniform(0, 0.34, MN), rng.uniform(-0.01, 0.01, MN)))
         sensor = c_oracle.evaluate(model, Ptrue, offs, None, pts)["y"] + rng.normal(0, 0.05, (MN, 2))
         P0 = Ptrue * (1 + 1e-3 * rng.standard_normal(Ptrue.shape[0]))
-        np.savez("/tmp/fuzz_in.npz", name=name, offs=offs, sensor=sensor, pts=pts, P0=P0)
+        np.savez(fin, name=name, offs=offs, sensor=sensor, pts=pts, P0=P0)
         ref = c_oracle.step(model, P0, offs, sensor, pts, 1e-3)
         outs = {}
         for form, ipw, head in itertools.product(("tile", "block"), ("1", "2", "3", "4"), ("narrow", "wide")):
             if form == "block" and ipw != "1":
                 continue                      # several views per wave exist for the tile forms only
-            env = dict(os.environ, FUZZ_ROOT=ROOT, FUZZ_IN="/tmp/fuzz_in.npz", FUZZ_OUT="/tmp/fuzz_out.npz",
+            env = dict(os.environ, FUZZ_ROOT=ROOT, FUZZ_IN=fin, FUZZ_OUT=fout,
                        CALIB_GRAM_FORM=form, CALIB_ITEMS_PER_WAVE=ipw, CALIB_HEAD_LOADS=head, CALIB_FUSED_STREAM="0")
             subprocess.run([sys.executable, "-c", CHILD], env=env, check=True)
-            outs[(form, ipw, head)] = dict(np.load("/tmp/fuzz_out.npz"))
+            outs[(form, ipw, head)] = dict(np.load(fout))
         n0 = int(sizes[0])
         if np.all(sizes == n0) and n0 % 4 == 0 and n0 >= 64:
             # stream form: 1 .. M waves (a share is at least one view), both head-load forms
             for waves, head in itertools.product(sorted({1, max(1, M // 3), max(1, int(rng.integers(1, M + 1))), M}), ("narrow", "wide")):
-                env = dict(os.environ, FUZZ_ROOT=ROOT, FUZZ_IN="/tmp/fuzz_in.npz", FUZZ_OUT="/tmp/fuzz_out.npz",
+                env = dict(os.environ, FUZZ_ROOT=ROOT, FUZZ_IN=fin, FUZZ_OUT=fout,
                            CALIB_FUSED_STREAM="1", CALIB_STREAM_WAVES=str(waves), CALIB_HEAD_LOADS=head)
                 subprocess.run([sys.executable, "-c", CHILD], env=env, check=True)
-                outs[("stream", str(waves), head)] = dict(np.load("/tmp/fuzz_out.npz"))
+                outs[("stream", str(waves), head)] = dict(np.load(fout))
         base = outs[("tile", "1", "narrow")]
         for key, o in outs.items():
             for k in ("E", "V"):                                   # per-view blocks
@@ -81,6 +85,7 @@ def main():
             assert err < 1e-7, (t, key, "delta vs oracle", err)
         print(f"trial {t}: {name}, {M} views, {MN} points, sizes {sizes.min()}..{sizes.max()}: {len(outs)} variants agree; "
               f"step vs C oracle {max(np.linalg.norm(o['delta'] - ref) / np.linalg.norm(ref) for o in outs.values()):.1e}", flush=True)
+    shutil.rmtree(tmp, ignore_errors=True)
     print(f"ok: {trials} trials, worst step error vs the C oracle {worst:.2e}")
 
 

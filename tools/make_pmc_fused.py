@@ -7,13 +7,14 @@ profiles/<round>_<workload>_pmc.json from the counter passes of tools/pmc_pass.s
 --batches = 64-lane batches one fused launch evaluates (one view item per wave: views x ceil(points per view / 64);
 stream form: the sum over the waves of ceil(points of the wave's share / 64)). Without --batches the count is derived
 from the launch shape the profiled build reported for this shard -- `config.fused_form` {share, waves} and the shard's
-views x points in gpurun_out/prof/bench_<tag>.json -- and share / waves are recorded, so that bench.py can tell when it
+views x points in $PROFILE_OUT/prof/bench_<tag>.json -- and share / waves are recorded, so that bench.py can tell when it
 runs with another launch width (another CU count, CALIB_STREAM_WAVES) than the counters were taken at.
 Counters are the mean over the dispatches of a kernel; FETCH_SIZE / WRITE_SIZE come in KiB, and on gfx950
 FETCH_SIZE counts 64 B per 128-B request of a wide coalesced read, so it is doubled (MI355X_MICROARCH.md, HBM)."""
 import argparse, csv, glob, json, os, subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT = os.environ.get("PROFILE_OUT") or os.path.join(ROOT, "profile_out")      # as tools/profile_round.sh
 
 
 def short(n):
@@ -22,12 +23,12 @@ def short(n):
 
 def collect(tag):
     """mean per dispatch of every counter per kernel: from the compact file tools/pmc_compact.py wrote on the GPU box
-    (gpurun_out/prof/pmc_<tag>.json), else from the raw counter_collection.csv files"""
-    compact = os.path.join(ROOT, "gpurun_out", "prof", f"pmc_{tag}.json")
+    ($PROFILE_OUT/prof/pmc_<tag>.json), else from the raw counter_collection.csv files"""
+    compact = os.path.join(OUT, "prof", f"pmc_{tag}.json")
     if os.path.exists(compact):
         return json.load(open(compact))
     acc = {}
-    for f in sorted(glob.glob(os.path.join(ROOT, f"gpurun_out/pmc_{tag}_*/**/*counter_collection.csv"), recursive=True)):
+    for f in sorted(glob.glob(os.path.join(OUT, f"pmc_{tag}_*/**/*counter_collection.csv"), recursive=True)):
         per = {}
         for r in csv.DictReader(open(f)):
             key = (short(r["Kernel_Name"]), r["Counter_Name"], r["Dispatch_Id"])
@@ -62,7 +63,7 @@ def main():
     k = collect(a.tag)
     form = None
     if a.batches <= 0:
-        line = json.loads(open(os.path.join(ROOT, "gpurun_out", "prof", f"bench_{a.tag}.json")).read())
+        line = json.loads(open(os.path.join(OUT, "prof", f"bench_{a.tag}.json")).read())
         cfg = line["config"]
         form = cfg["fused_form"]
         views, n = int(cfg["views_per_gpu"]), int(cfg["points_per_view"])

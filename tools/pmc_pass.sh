@@ -3,6 +3,8 @@
 # One rocprofv3 --pmc pass per counter group (<= 8 SQ counters, FETCH_SIZE and WRITE_SIZE on their own), kernel trace
 # only; summaries by tools/pmc_summary.py / tools/make_pmc_fused.py.
 R=${GRAFT_REPO_ROOT:-/root/repo}
+export PROFILE_OUT=$(realpath -m "${PROFILE_OUT:-$R/profile_out}")      # outputs of the profiling tools
+mkdir -p "$PROFILE_OUT"
 TAG=$1; shift
 export TMPDIR=/tmp
 cd /tmp
@@ -14,8 +16,9 @@ G5="FETCH_SIZE"
 G6="WRITE_SIZE"
 n=1
 for G in "$G1" "$G2" "$G3" "$G4" "$G5" "$G6"; do
-  rocprofv3 --kernel-trace --pmc $G --output-format csv -d $R/gpurun_out/pmc_${TAG}_$n -- python3 $R/bench.py --no-cpu-baseline --no-api --steps 10 --warmup 2 --min-seconds 0.05 "$@" > $R/gpurun_out/pmc_${TAG}_$n.log 2>&1
-  find $R/gpurun_out/pmc_${TAG}_$n -name "*kernel_trace.csv" -delete
+  rocprofv3 --kernel-trace --pmc $G --output-format csv -d $PROFILE_OUT/pmc_${TAG}_$n -- python3 $R/bench.py --full --no-cpu-baseline --no-api --steps 10 --warmup 2 --min-seconds 0.05 "$@" > $PROFILE_OUT/pmc_${TAG}_$n.log 2>&1 \
+    || { echo "pmc $TAG pass $n failed"; tail -5 $PROFILE_OUT/pmc_${TAG}_$n.log; exit 1; }
+  find $PROFILE_OUT/pmc_${TAG}_$n -name "*kernel_trace.csv" -delete
   echo "pmc $TAG pass $n done"
   n=$((n+1))
 done

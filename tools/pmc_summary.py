@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """Mean per-dispatch value of every counter for kernels whose name contains a substring, from the
-counter_collection.csv files under gpurun_out/pmc_<tag>_*: python tools/pmc_summary.py <tag> [substring]"""
-import csv, glob, sys
+counter_collection.csv files under $PROFILE_OUT/pmc_<tag>_*: python tools/pmc_summary.py <tag> [substring]"""
+import csv, glob, os, sys
+OUT = os.environ.get("PROFILE_OUT") or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profile_out")
 tag = sys.argv[1]
 pat = sys.argv[2] if len(sys.argv) > 2 else "fused"
 acc = {}
-for f in sorted(glob.glob(f"gpurun_out/pmc_{tag}_*/**/*counter_collection.csv", recursive=True)):
+for f in sorted(glob.glob(os.path.join(OUT, f"pmc_{tag}_*/**/*counter_collection.csv"), recursive=True)):
     per = {}
     for r in csv.DictReader(open(f)):
         if pat not in r["Kernel_Name"]:
