@@ -3,6 +3,7 @@
 #include "../../include/calib_lm.h"
 #include "kernels.hpp"
 #include "host_rows.hpp"
+#include "launch_plan.hpp"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -116,19 +117,9 @@ struct calib_handle_s {
     int n_items = 0;
     int64_t n_tiles = 0;
     int max_views_per_tile = 1;
-    int schur_blocks = 1;
-    int gram_wpi = 1;             // waves per gram item (two-kernel mode)
-    int fused_wpi = 1;            // waves per item of the fused kernel
     int uniform_n = 0;            // > 0: every item is one whole view of exactly this many points, in order (item i = view i = points [i n, (i+1) n))
-    int head_loads = 0;           // per-view kernels' record-head loads: 0 = by shard size, 1 = one load per value, 2 = coalesced + DPP (CALIB_HEAD_LOADS)
-    int items_per_wave = 0;       // fused kernel, short uniform items: 0 = chosen per shard (CALIB_ITEMS_PER_WAVE)
-    int upd_lane_views = 0;       // shards from this many views on take update_backsub_lane_kernel (CALIB_UPD_LANE_VIEWS)
-    int upd_small_views = 0;      // shards up to this many views take update_backsub_small_kernel (CALIB_UPD_SMALL_VIEWS)
-    int gram_form = 0;            // fp64 fused kernel: 0 = chosen per shard, 1 = 16x16x4 tiles, 2 = 4x4x4 blocks (CALIB_GRAM_FORM)
-    int stream_mode = -1;         // fused_stream_kernel: -1 = chosen per shard, 0 = never, 1 = whenever the shard allows it (CALIB_FUSED_STREAM)
-    int stream_waves_env = 0;     // > 0: waves of the stream launch (CALIB_STREAM_WAVES); 0 = the chip's wave slots
-    int stream_share = 0;         // > 0: this problem's fused rounds run in stream form, `stream_share` 4-point groups per wave
-    int stream_waves = 0;         // waves that have work = overflow records behind the nv view records
+    Knobs knobs;                  // CALIB_* tuning variables (calib_create)
+    LaunchPlan plan;              // kernel forms and grids of this problem's LM rounds (plan_of)
     // LM rounds walk the points in chunks of whole views so that a chunk's compact J
     // (written by the jacobian kernel, read once by the gram kernel) can stay on-die
     struct Chunk { int64_t p0, p1; int item0, item1; };
@@ -346,11 +337,11 @@ template <typename T, int C>
 int launch_gram_t(calib_handle_s* h, const LMState* st, int sel, int item0, int item1, int64_t origin) {
     using T2 = typename Pair<T>::type;
     if (item1 <= item0) return CALIB_OK;
-    const int ipb = 4 / h->gram_wpi;       // items per workgroup
+    const int ipb = 4 / h->plan.gram_wpi;  // items per workgroup
     const int blocks = (item1 - item0 + ipb - 1) / ipb;
     launch_kind(h, 1, gram_kernel<T, C>, dim3(blocks), dim3(256), 0,
                 reinterpret_cast<const T2*>(h->J.p), reinterpret_cast<const T2*>(h->r.p),
-                (const int64_t*)h->item_pt0.p, (const int*)h->item_n.p, item0, item1, origin, h->gram_wpi, st, sel, h->G[0].p,
+                (const int64_t*)h->item_pt0.p, (const int*)h->item_n.p, item0, item1, origin, h->plan.gram_wpi, st, sel, h->G[0].p,
                 h->G[1].p, h->bpart.p, h->n_bpart);
     h->n_bpart += blocks;                  // the chunk's workgroups append their partials
     LAUNCHED(h, "gram_kernel");
@@ -368,69 +359,48 @@ int launch_gram(calib_handle_s* h, const LMState* st, int sel, int item0, int it
 template <int MODEL, typename T>
 int launch_fused_t(calib_handle_s* h, const LMState* st, int sel) {
     using T2 = typename Pair<T>::type;
-    if (h->n_items == 0) return CALIB_OK;
-    // ROWS = 32, 4 waves per workgroup: the 64-row / 2-wave variants measured 1-6 % slower (c3, c5, c2)
-    const int wpi = std::min(h->fused_wpi, 4);
-    const bool g44 = sizeof(T) == 8 && (h->gram_form == 2 || (h->gram_form == 0 && h->MN > (int64_t)128 * h->n_items));
-    // short uniform items (tile forms, one wave each): on shards large enough to leave every workgroup slot of the
-    // chip (4 per CU) four workgroups even so, a wave takes up to four items in a row -- one prologue, one partial,
-    // one barrier, the next item's points requested early (c5 shard -7 %; c4's 12 500 items: no gain, c2: slower)
-    int ipw = 1;
-    if (!g44 && wpi == 1 && h->uniform_n > 0) {
-        if (h->items_per_wave > 0) ipw = h->items_per_wave;
-        else while (ipw < 4 && h->n_items / (8 * ipw) >= 16 * h->num_cus) ipw *= 2;
-    }
-    const int ipb = (4 / wpi) * ipw;
-    const int blocks = (h->n_items + ipb - 1) / ipb;
-    // fp64 items of more than two batches build J^T J from 4x4 blocks (v_mfma_f64_4x4x4_4b, symmetric half only;
-    // c3 -4.5 %); shorter items stay on the 16x16x4 form, whose record goes to HBM straight from the accumulators
-    // (one-batch items: c2 +4 % on the block form; two batches, c5: no difference)
+    const LaunchPlan& p = h->plan;
+    if (p.fused_blocks == 0) return CALIB_OK;
     auto launch = [&](auto kernel) {
-        launch_kind(h, 2, kernel, dim3(blocks), dim3(256), 0, (const double*)h->P[0].p,
+        launch_kind(h, 2, kernel, dim3(p.fused_blocks), dim3(256), 0, (const double*)h->P[0].p,
                     (const double*)h->P[1].p, reinterpret_cast<const T2*>(h->uv.p), reinterpret_cast<const T2*>(h->XY.p),
                     reinterpret_cast<const T*>(h->Z.p), reinterpret_cast<const T*>(h->VC.p), (const int64_t*)h->item_pt0.p,
-                    (const int*)h->item_n.p, (const int*)h->item_view.p, h->n_items, h->uniform_n, ipw, wpi,
+                    (const int*)h->item_n.p, (const int*)h->item_view.p, h->n_items, h->uniform_n, p.ipw, p.fused_wpi,
                     (const uint32_t*)h->emit_tab.p, st, sel, h->G[0].p, h->G[1].p, h->bpart.p);
     };
-    if constexpr (sizeof(T) == 8) {
-        if (g44) launch(fused_kernel<MODEL, T, 32, 4, true, false>);
-        else if (ipw > 1) launch(fused_kernel<MODEL, T, 32, 4, false, true>);
-        else launch(fused_kernel<MODEL, T, 32, 4, false, false>);
-    } else {
-        if (ipw > 1) launch(fused_kernel<MODEL, T, 32, 4, false, true>);
-        else launch(fused_kernel<MODEL, T, 32, 4, false, false>);
-    }
-    h->n_bpart = blocks;
+    if (p.fused == FusedForm::Tile) launch(fused_kernel<MODEL, T, 32, 4, false, false>);
+    else if (p.fused == FusedForm::TileMulti) launch(fused_kernel<MODEL, T, 32, 4, false, true>);
+    else if constexpr (sizeof(T) == 8) launch(fused_kernel<MODEL, T, 32, 4, true, false>);    // Block44: fp64 only
+    h->n_bpart = p.fused_blocks;
     LAUNCHED(h, "fused_kernel");
     return CALIB_OK;
 }
 
 // records of this problem's fused rounds: stream form (view records + one overflow record per wave) or one per item
-bool stream_rounds(const calib_handle_s* h) { return h->lm_mode == CALIB_LM_FUSED && h->stream_share > 0; }
 StreamMap stream_map(const calib_handle_s* h) {
     StreamMap sm;
-    sm.share = stream_rounds(h) ? h->stream_share : 0;
+    sm.share = h->plan.stream_share;
     sm.n4 = h->uniform_n / 4;
     sm.nv = h->nv;
     return sm;
 }
-int num_records(const calib_handle_s* h) { return std::max(h->n_items, 1) + h->stream_waves; }
+int num_records(const calib_handle_s* h) { return std::max(h->n_items, 1) + h->plan.stream_waves; }
 
 template <int MODEL>
 int launch_fused_stream(calib_handle_s* h, const LMState* st, int sel) {
-    const int blocks = (h->stream_waves + 3) / 4;
-    launch_kind(h, 2, fused_stream_kernel<MODEL>, dim3(blocks), dim3(256), 0, (const double*)h->P[0].p, (const double*)h->P[1].p,
+    const LaunchPlan& p = h->plan;
+    launch_kind(h, 2, fused_stream_kernel<MODEL>, dim3(p.fused_blocks), dim3(256), 0, (const double*)h->P[0].p, (const double*)h->P[1].p,
                 reinterpret_cast<const double2*>(h->uv.p), reinterpret_cast<const double2*>(h->XY.p),
                 reinterpret_cast<const double*>(h->Z.p), reinterpret_cast<const double*>(h->VC.p), h->uniform_n,
-                h->nv, h->stream_share, (const uint32_t*)h->emit_tab.p, (const int32_t*)h->stream_ops.p, st, sel, h->G[0].p, h->G[1].p,
+                h->nv, p.stream_share, (const uint32_t*)h->emit_tab.p, (const int32_t*)h->stream_ops.p, st, sel, h->G[0].p, h->G[1].p,
                 h->bpart.p);
-    h->n_bpart = blocks;
+    h->n_bpart = p.fused_blocks;
     LAUNCHED(h, "fused_stream_kernel");
     return CALIB_OK;
 }
 
 int launch_fused(calib_handle_s* h, const LMState* st, int sel) {
-    if (stream_rounds(h))
+    if (h->plan.fused == FusedForm::Stream)
         return h->model == CALIB_MODEL_RADTAN ? launch_fused_stream<kRadtan>(h, st, sel)
                                               : launch_fused_stream<kFisheye>(h, st, sel);
     if (h->dtype == CALIB_DTYPE_F64)
@@ -458,31 +428,17 @@ PeerExchange next_exchange(calib_handle_s* h) {
     return x;
 }
 
-// shards above this many views load record heads in the coalesced, DPP-broadcast form (kernels.hpp: load_view_head).
-// Round 4: since a record is six rows (768 B) the broadcast chain behind the loads is 48 DPP moves instead of 54, and on
-// c4's 12 500-view shard the wide update kernel (122 VGPRs, no scratch) is as fast as the narrow one was WITH its 12-byte
-// spill (10.1 vs 10.3 us; the narrow one without the spill, at three workgroups per CU: 12.3 us -- 782 workgroups on 768
-// slots are two rounds). So every shard the small update kernel does not take (> 4 096 views) loads wide; the narrow
-// forms remain for the small shards and on request (CALIB_HEAD_LOADS=narrow).
-constexpr int kWideHeadViews = 4096;
-
-// Larger shards, and shards whose views can be two records (stream form: the second record doubles the 27 per-value
-// loads of the narrow form; c3 schur +2.1 us, update +3 us -- six coalesced rows per record cost nothing extra)
-bool wide_heads(const calib_handle_s* h) {
-    return h->head_loads == 2 || (h->head_loads == 0 && (h->nv > kWideHeadViews || stream_rounds(h)));
-}
-
 int launch_schur(calib_handle_s* h, const LMState* st) {
-    dim3 grid(h->schur_blocks, 3);
+    const LaunchPlan& p = h->plan;
+    dim3 grid(p.schur_blocks, 3);
     auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, grid, dim3(kSchurBlock), 0, h->stream, h->G[0].p, h->G[1].p, st, view_items(h), h->nv,
                            stream_map(h), h->bpart.p, h->n_bpart, h->part.p);
     };
-    const bool wide = wide_heads(h), strm = stream_rounds(h);
     auto pick = [&](auto Lc) {
         constexpr int LL = decltype(Lc)::value;
-        if (strm) { if (wide) launch(schur_kernel<LL, true, true>); else launch(schur_kernel<LL, false, true>); }
-        else { if (wide) launch(schur_kernel<LL, true, false>); else launch(schur_kernel<LL, false, false>); }
+        if (p.stream()) { if (p.wide_heads) launch(schur_kernel<LL, true, true>); else launch(schur_kernel<LL, false, true>); }
+        else { if (p.wide_heads) launch(schur_kernel<LL, true, false>); else launch(schur_kernel<LL, false, false>); }
     };
     if (h->L == 10) pick(std::integral_constant<int, 10>{}); else pick(std::integral_constant<int, 9>{});
     LAUNCHED(h, "schur_kernel");
@@ -496,7 +452,7 @@ int launch_schur_reduce(calib_handle_s* h, const LMState* st, double* red) {
         if (rc) return rc;
     }
     hipLaunchKernelGGL(reduce_kernel, dim3(2 * VA), dim3(64), 0, h->stream, h->part.p,
-                       h->nv > 0 ? h->schur_blocks : 0, VA, st, red,
+                       h->nv > 0 ? h->plan.schur_blocks : 0, VA, st, red,
                        h->exchange_round ? next_exchange(h) : PeerExchange{});
     LAUNCHED(h, "reduce_kernel");
     return CALIB_OK;
@@ -507,56 +463,45 @@ int launch_schur_reduce(calib_handle_s* h, const LMState* st, double* red) {
 LMState* st_cur(calib_handle_s* h) { return h->st.p + (h->rounds_enqueued & 1); }
 LMState* st_next(calib_handle_s* h) { return h->st.p + ((h->rounds_enqueued + 1) & 1); }
 
-// shards of at most this many views take the latency-oriented form of the update kernel (kernels.hpp)
-constexpr int kUpdSmallViews = 4096;
-// shards of at least this many views take the one-lane-per-view form (a wave per 64 views: it needs many to fill the chip).
-// tools/sweep_upd_lane.sh, update kernel us, 16 lanes per view / one lane per view: 10 000 views 8.9 / 15.0 - 12 500 (fp32)
-// 10.0 / 11.5 - 16 384: 11.2 / 12.4 - 32 768: 19.0 / 13.3 - 65 536: 29.7 / 17.6 - 125 000: 47.5 / 30.5
-constexpr int kUpdLaneViews = 24576;
-
 template <int L, typename T>
 int launch_update_backsub_t(calib_handle_s* h) {
-    if (h->nv <= h->upd_small_views) {
-        const int blocks = std::max(1, (h->nv + kUpdViewsPerBlock - 1) / kUpdViewsPerBlock);    // one view per 16-lane group
-        auto launchSmall = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kUpdThreads), 0, h->stream,
-                               h->G[0].p, h->G[1].p, st_cur(h), st_next(h), h->red, view_items(h), h->view_ext.p, h->nv,
-                               stream_map(h), h->P[0].p, h->P[1].p, h->trace.p, reinterpret_cast<T*>(h->VC.p));
-        };
-        if (stream_rounds(h)) launchSmall(update_backsub_small_kernel<L, T, true>);
-        else launchSmall(update_backsub_small_kernel<L, T, false>);
-        LAUNCHED(h, "update_backsub_small_kernel");
+    const LaunchPlan& p = h->plan;
+    UpdArgs<T> a;
+    a.G0 = h->G[0].p; a.G1 = h->G[1].p;
+    a.st_in = st_cur(h); a.st_out = st_next(h);
+    a.red = h->red;
+    a.view_item0 = view_items(h);
+    a.view_ext = h->view_ext.p;
+    a.nv = h->nv;
+    a.sm = stream_map(h);
+    a.P0 = h->P[0].p; a.P1 = h->P[1].p;
+    a.trace = h->trace.p;
+    a.VC = reinterpret_cast<T*>(h->VC.p);
+    auto launch = [&](auto kernel, int threads, const char* name) -> int {
+        hipLaunchKernelGGL(kernel, dim3(p.update_blocks), dim3(threads), 0, h->stream, a);
+        LAUNCHED(h, name);
         return CALIB_OK;
-    }
-    if (h->nv >= h->upd_lane_views && h->head_loads == 0) {
-        const int blocks = std::max(1, std::min(12 * h->num_cus, (h->nv + kSchurThreads - 1) / kSchurThreads));
-        auto launchLane = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kSchurThreads), 0, h->stream,
-                               h->G[0].p, h->G[1].p, st_cur(h), st_next(h), h->red, view_items(h), h->view_ext.p, h->nv,
-                               stream_map(h), h->P[0].p, h->P[1].p, h->trace.p, reinterpret_cast<T*>(h->VC.p));
-        };
-        if (stream_rounds(h)) launchLane(update_backsub_lane_kernel<L, T, true>);
-        else launchLane(update_backsub_lane_kernel<L, T, false>);
-        LAUNCHED(h, "update_backsub_lane_kernel");
-        return CALIB_OK;
-    }
-    const int per = kSchurThreads / 16;
-    const int blocks = std::max(1, std::min(2048, (h->nv + per - 1) / per));     // grid-stride over views
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kSchurThreads), 0, h->stream, h->G[0].p,
-                           h->G[1].p, st_cur(h), st_next(h), h->red, view_items(h), h->view_ext.p, h->nv,
-                           stream_map(h), h->P[0].p, h->P[1].p, h->trace.p, reinterpret_cast<T*>(h->VC.p));
     };
-    if (stream_rounds(h)) { if (wide_heads(h)) launch(update_backsub_kernel<L, T, true, true>); else launch(update_backsub_kernel<L, T, false, true>); }
-    else { if (wide_heads(h)) launch(update_backsub_kernel<L, T, true, false>); else launch(update_backsub_kernel<L, T, false, false>); }
-    LAUNCHED(h, "update_backsub_kernel");
-    return CALIB_OK;
+    if (p.update == UpdateForm::Small)
+        return p.stream() ? launch(update_backsub_small_kernel<L, T, true>, kUpdThreads, "update_backsub_small_kernel")
+                          : launch(update_backsub_small_kernel<L, T, false>, kUpdThreads, "update_backsub_small_kernel");
+    if (p.update == UpdateForm::Lane)
+        return p.stream() ? launch(update_backsub_lane_kernel<L, T, true>, kSchurThreads, "update_backsub_lane_kernel")
+                          : launch(update_backsub_lane_kernel<L, T, false>, kSchurThreads, "update_backsub_lane_kernel");
+    return p.stream() ? launch(update_backsub_kernel<L, T, true>, kSchurThreads, "update_backsub_kernel")
+                      : launch(update_backsub_kernel<L, T, false>, kSchurThreads, "update_backsub_kernel");
 }
 
 int launch_update_backsub(calib_handle_s* h) {
     if (h->dtype == CALIB_DTYPE_F64)
         return h->L == 10 ? launch_update_backsub_t<10, double>(h) : launch_update_backsub_t<9, double>(h);
     return h->L == 10 ? launch_update_backsub_t<10, float>(h) : launch_update_backsub_t<9, float>(h);
+}
+
+LaunchPlan plan_of(const calib_handle_s* h) {
+    ShardShape s;
+    s.nv = h->nv; s.n_items = h->n_items; s.uniform_n = h->uniform_n; s.MN = h->MN;
+    return makePlan(s, h->dtype, h->lm_mode, h->knobs, h->num_cus);
 }
 
 int need_problem(calib_handle_s* h) {
@@ -637,16 +582,8 @@ int calib_create(int model, int dtype, int device_id, calib_handle_t* out_handle
             return fail(CALIB_E_HIP, std::string("stream record table: ") + (built ? hipGetErrorString(e) : "inconsistent"));
         }
     }
-    if (const char* e = std::getenv("CALIB_LM_MODE")) h->lm_mode = std::atoi(e) ? CALIB_LM_TWO_KERNEL : CALIB_LM_FUSED;
-    if (const char* e = std::getenv("CALIB_HEAD_LOADS")) h->head_loads = std::strcmp(e, "narrow") == 0 ? 1 : (std::strcmp(e, "wide") == 0 ? 2 : 0);
-    if (const char* e = std::getenv("CALIB_ITEMS_PER_WAVE")) h->items_per_wave = std::max(0, std::min(16, std::atoi(e)));
-    h->upd_lane_views = kUpdLaneViews;
-    if (const char* e = std::getenv("CALIB_UPD_LANE_VIEWS")) h->upd_lane_views = std::max(1, std::atoi(e));
-    h->upd_small_views = kUpdSmallViews;
-    if (const char* e = std::getenv("CALIB_UPD_SMALL_VIEWS")) h->upd_small_views = std::max(0, std::atoi(e));
-    if (const char* e = std::getenv("CALIB_GRAM_FORM")) h->gram_form = std::strcmp(e, "tile") == 0 ? 1 : (std::strcmp(e, "block") == 0 ? 2 : 0);
-    if (const char* e = std::getenv("CALIB_FUSED_STREAM")) h->stream_mode = std::atoi(e) > 0 ? 1 : (std::atoi(e) == 0 ? 0 : -1);
-    if (const char* e = std::getenv("CALIB_STREAM_WAVES")) h->stream_waves_env = std::max(0, std::atoi(e));
+    h->knobs = readKnobs();
+    h->lm_mode = h->knobs.lm_mode;
     {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_id) == hipSuccess && cus > 0)
@@ -727,13 +664,14 @@ int calib_set_lm_mode(calib_handle_t h, int mode) {
     if (mode != CALIB_LM_FUSED && mode != CALIB_LM_TWO_KERNEL) return fail(CALIB_E_INVALID, "unknown LM mode");
     if (h->lm_active) return fail(CALIB_E_STATE, "cannot change the LM mode inside a run");
     h->lm_mode = mode;
+    if (h->has_problem) h->plan = plan_of(h);      // the stream form exists in fused mode only
     return CALIB_OK;
 }
 
 int calib_fused_form(calib_handle_t h, int* out_share, int* out_waves) {
     if (!h || !out_share || !out_waves) return fail(CALIB_E_INVALID, "null argument");
-    *out_share = stream_rounds(h) ? h->stream_share : 0;
-    *out_waves = stream_rounds(h) ? h->stream_waves : 0;
+    *out_share = h->plan.stream_share;
+    *out_waves = h->plan.stream_waves;
     return CALIB_OK;
 }
 
@@ -797,7 +735,7 @@ int set_problem_impl(calib_handle_t h, int64_t num_views, const int64_t* view_of
     h->M = num_views;
     h->MN = MN;
 
-    const bool timing = std::getenv("CALIB_TIMING") != nullptr;
+    const bool timing = h->knobs.timing;
     auto tnow = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double tmark = tnow();
     auto lap = [&](const char* what) { if (timing) { const double t = tnow(); std::fprintf(stderr, "  set_problem %-28s %.3f ms\n", what, t - tmark); tmark = t; } };
@@ -825,17 +763,6 @@ int set_problem_impl(calib_handle_t h, int64_t num_views, const int64_t* view_of
     h->n_items = (int)item_pt0.size();
     // compact view of point p (points of the non-empty views are contiguous)
     auto viewOf = [&](int64_t p) { return (int)(std::upper_bound(voffs.begin(), voffs.end(), p) - voffs.begin()) - 1; };
-    {   // waves per gram item from the mean points per item: a wave wants >= 2 trips of 16 points
-        const double avg = h->n_items ? (double)MN / h->n_items : 0.0;
-        h->gram_wpi = avg >= 128 ? 4 : (avg >= 64 ? 2 : 1);
-        // fused kernel: one wave per item is fastest (measured c3: 84 us vs 102 us at 4) as long as
-        // there are enough items to fill the chip; few big items are split over more waves
-        h->fused_wpi = h->n_items >= 2048 ? 1 : h->gram_wpi;
-        if (const char* e = std::getenv("CALIB_GRAM_WPI")) {      // tuning knob
-            const int w = std::atoi(e);
-            if (w == 1 || w == 2 || w == 4) h->gram_wpi = h->fused_wpi = w;
-        }
-    }
     h->n_tiles = (MN + kTile - 1) / kTile;
     int mv = 1;
     {   // views spanned by a 256-point tile (what the jacobian kernel stages in LDS): one sweep over the offsets
@@ -852,8 +779,7 @@ int set_problem_impl(calib_handle_t h, int64_t num_views, const int64_t* view_of
         // Measured on MI355X (c3, 2 M points): chunks small enough for the 256 MiB Infinity Cache
         // do NOT make the J round trip cheaper (0.33 ms/iter at one chunk, 0.45 at 262 k points,
         // 1.1 at 65 k), so the chunk only bounds the J buffer: 64 M points = 17 GB at C = 16, fp64.
-        int64_t target = (int64_t)1 << 26;
-        if (const char* e = std::getenv("CALIB_CHUNK_POINTS")) target = std::max<int64_t>(1, std::atoll(e));
+        const int64_t target = h->knobs.chunk_points;
         h->chunks.clear();
         h->max_chunk_points = 0;
         int v = 0;
@@ -880,8 +806,6 @@ int set_problem_impl(calib_handle_t h, int64_t num_views, const int64_t* view_of
         }
     }
     h->max_views_per_tile = mv;
-    const int per = kSchurViewsPerBlock;
-    h->schur_blocks = std::max(1, std::min(kMaxSchurBlocks, (h->nv + per - 1) / per));
 
     lap("host view/item lists");
     const size_t ts = tsize(h);
@@ -914,24 +838,7 @@ int set_problem_impl(calib_handle_t h, int64_t num_views, const int64_t* view_of
             if (item_n[i] != un || item_pt0[i] != (int64_t)i * un || item_view[i] != (int)i) un = 0;
         h->uniform_n = un;
     }
-    {
-        // Stream form of the fused kernel (kernels.hpp: fused_stream_kernel): uniform fp64 shards whose views are whole
-        // 4-point groups and at least one batch long. One wave per wave slot of the chip (4 per SIMD), every wave the
-        // same share of groups; a share is at least two views, so a view is cut by at most one wave start. By default
-        // only where a wave gets two views or more anyway (below that, a view per wave fills the chip better).
-        h->stream_share = h->stream_waves = 0;
-        const int un = h->uniform_n;
-        const bool can = h->dtype == CALIB_DTYPE_F64 && un >= 64 && (un & 3) == 0 && MN < ((int64_t)1 << 31) && h->nv >= 1;
-        if (can && h->stream_mode != 0) {
-            const int slots = h->stream_waves_env > 0 ? h->stream_waves_env : 4 * CALIB_STREAM_MIN_BLOCKS * h->num_cus;
-            const int waves = std::max(1, std::min(slots, h->nv));
-            if (h->stream_mode == 1 || h->nv >= 2 * slots) {
-                const int64_t groups = (int64_t)h->nv * (un / 4);
-                h->stream_share = (int)((groups + waves - 1) / waves);
-                h->stream_waves = (int)((groups + h->stream_share - 1) / h->stream_share);
-            }
-        }
-    }
+    h->plan = plan_of(h);
     HIP_TRY(upload(h->item_n.p, item_n.data(), item_n.size() * 4));
     HIP_TRY(upload(h->item_view.p, item_view.data(), item_view.size() * 4));
     HIP_TRY(upload(h->item_pt0.p, item_pt0.data(), item_pt0.size() * 8));
@@ -1075,7 +982,7 @@ int calib_lm_begin(calib_handle_t h, const double* P0, int max_iters, double lam
         if (fresh) HIP_TRY(hipMemsetAsync(h->G[b].p, 0, h->G[b].n * 8, h->stream));
     }
     HIP_TRY(h->bpart.alloc(((size_t)std::max(h->n_items, 1) + h->chunks.size()) * kPartStride));   // <= 1 per item (+1 per chunk)
-    HIP_TRY(h->part.alloc((size_t)2 * h->schur_blocks * variantSize(h->L)));
+    HIP_TRY(h->part.alloc((size_t)2 * h->plan.schur_blocks * variantSize(h->L)));
     HIP_TRY(h->red_own.alloc((size_t)reduceSize(h->L)));
     if (!h->red) h->red = h->red_own.p;
     HIP_TRY(h->P[0].alloc((size_t)K));

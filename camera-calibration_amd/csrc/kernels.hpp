@@ -1205,6 +1205,18 @@ __host__ __device__ __forceinline__ int stream_extra_item(const StreamMap& sm, i
     return w * (unsigned)sm.share > first ? sm.nv + (int)w : -1;
 }
 
+// The records of view v: items [i0, i0 + nitems) and, in stream form, the overflow record `extra` (-1: none).
+// view_item0 == nullptr: every view is a single item (item index == view index).
+struct ViewSpan { int i0, nitems, extra; };
+template <bool STREAM>
+__device__ __forceinline__ ViewSpan view_span(const int* __restrict__ view_item0, const StreamMap& sm, int v) {
+    ViewSpan s;
+    s.i0 = view_item0 ? view_item0[v] : v;
+    s.nitems = view_item0 ? view_item0[v + 1] - s.i0 : 1;
+    s.extra = STREAM ? stream_extra_item(sm, v) : -1;
+    return s;
+}
+
 // ---------------------------------------------------------------- per-view elimination
 // 16 lanes per view, working from the head of the view's record(s): lane c < L owns row c of E, lane L the view gradient.
 __device__ __forceinline__ constexpr int tri(int m, int n) { return m * (m + 1) / 2 + n; }
@@ -1235,18 +1247,17 @@ __device__ __forceinline__ double row_bcast(double v) {
 // lanes -- more work for the address coalescer, but no chain of 54 DPP moves behind the loads (c3 / c4 -0.9 us).
 // WIDE form in two steps, so that a kernel can have the next view's rows in flight while it factors this one:
 // the raw column-c elements of the six rows and of the gradient row (summed over the view's items) ...
-__device__ __forceinline__ void request_head_rows(const double* __restrict__ G, int item0, int nitems, int extra, int c,
-                                                  double (&r)[6]) {
-    const double* g = G + (int64_t)item0 * kGStride;
+__device__ __forceinline__ void request_head_rows(const double* __restrict__ G, const ViewSpan& s, int c, double (&r)[6]) {
+    const double* g = G + (int64_t)s.i0 * kGStride;
 #pragma unroll
     for (int m = 0; m < 6; ++m) r[m] = g[kGRows + m * 16 + c];
-    for (int it = 1; it < nitems; ++it) {                     // > 1 item only for views above kGramChunk points
+    for (int it = 1; it < s.nitems; ++it) {                   // > 1 item only for views above kGramChunk points
         g += kGStride;
 #pragma unroll
         for (int m = 0; m < 6; ++m) r[m] += g[kGRows + m * 16 + c];
     }
-    if (extra >= 0) {                                         // stream form: the part of the view a second wave summed
-        g = G + (int64_t)extra * kGStride;
+    if (s.extra >= 0) {                                       // stream form: the part of the view a second wave summed
+        g = G + (int64_t)s.extra * kGStride;
 #pragma unroll
         for (int m = 0; m < 6; ++m) r[m] += g[kGRows + m * 16 + c];
     }
@@ -1269,43 +1280,40 @@ __device__ __forceinline__ void expand_head_rows(const double (&r)[6], int c, do
     }
 }
 
+// Narrow form, one record g: V's entries and this lane's right-hand side -- row c of E at m * 16 + c, or g_v at
+// gvSlot(L, m) = L + 1 + m (m < 5), 16 + L + 2. The first record assigns, later ones add (0.0 + x is not x for x = -0.0).
+template <int L, bool FIRST>
+__device__ __forceinline__ void add_head_record(const double* __restrict__ g, int c, double (&V)[21], double (&b)[6]) {
+    const int boff = c < L ? kGRows + c : gvSlot(L, 0);
+    const int bstep = c < L ? 16 : 1;
+    const int b5 = c < L ? kGRows + 5 * 16 + c : gvSlot(L, 5);
+#pragma unroll
+    for (int m = 0; m < 6; ++m) {
+#pragma unroll
+        for (int n = 0; n <= m; ++n) {
+            const double x = g[kGRows + m * 16 + L + n];
+            if (FIRST) V[tri(m, n)] = x; else V[tri(m, n)] += x;
+        }
+        const double x = g[m < 5 ? boff + m * bstep : b5];
+        if (FIRST) b[m] = x; else b[m] += x;
+    }
+}
+
 template <int L, bool WIDE>
-__device__ __forceinline__ void load_view_head(const double* __restrict__ G, int item0, int nitems, int extra, int c,
+__device__ __forceinline__ void load_view_head(const double* __restrict__ G, const ViewSpan& s, int c,
                                                double (&V)[21], double (&b)[6]) {
-    const double* g = G + (int64_t)item0 * kGStride;
     if constexpr (WIDE) {
         double r[6];
-        request_head_rows(G, item0, nitems, extra, c, r);
+        request_head_rows(G, s, c, r);
         expand_head_rows<L>(r, c, V, b);
     } else {
-        // this lane's right-hand side: row c of E at m * 16 + c, or g_v at gvSlot(L, m) = L + 1 + m (m < 5), 16 + L + 2
-        const int boff = c < L ? kGRows + c : gvSlot(L, 0);
-        const int bstep = c < L ? 16 : 1;
-        const int b5 = c < L ? kGRows + 5 * 16 + c : gvSlot(L, 5);
-#pragma unroll
-        for (int m = 0; m < 6; ++m) {
-#pragma unroll
-            for (int n = 0; n <= m; ++n) V[tri(m, n)] = g[kGRows + m * 16 + L + n];
-            b[m] = g[m < 5 ? boff + m * bstep : b5];
-        }
-        for (int it = 1; it < nitems; ++it) {                 // > 1 item only for views above kGramChunk points
+        const double* g = G + (int64_t)s.i0 * kGStride;
+        add_head_record<L, true>(g, c, V, b);
+        for (int it = 1; it < s.nitems; ++it) {               // > 1 item only for views above kGramChunk points
             g += kGStride;
-#pragma unroll
-            for (int m = 0; m < 6; ++m) {
-#pragma unroll
-                for (int n = 0; n <= m; ++n) V[tri(m, n)] += g[kGRows + m * 16 + L + n];
-                b[m] += g[m < 5 ? boff + m * bstep : b5];
-            }
+            add_head_record<L, false>(g, c, V, b);
         }
-        if (extra >= 0) {                                     // stream form: the part of the view a second wave summed
-            g = G + (int64_t)extra * kGStride;
-#pragma unroll
-            for (int m = 0; m < 6; ++m) {
-#pragma unroll
-                for (int n = 0; n <= m; ++n) V[tri(m, n)] += g[kGRows + m * 16 + L + n];
-                b[m] += g[m < 5 ? boff + m * bstep : b5];
-            }
-        }
+        if (s.extra >= 0) add_head_record<L, false>(G + (int64_t)s.extra * kGStride, c, V, b);   // stream form: the part of the view a second wave summed
     }
 }
 
@@ -1343,6 +1351,17 @@ __device__ __forceinline__ void forward6(const double (&V)[21], const double (&i
         z[m] = t * invd[m];
     }
 }
+// Lc^T d = w: the back substitution behind forward6 (V, invd from cholesky6)
+__device__ __forceinline__ void backward6(const double (&V)[21], const double (&invd)[6], const double (&w)[6],
+                                          double (&d)[6]) {
+#pragma unroll
+    for (int m = 5; m >= 0; --m) {
+        double t = w[m];
+#pragma unroll
+        for (int n = m + 1; n < 6; ++n) t -= V[tri(n, m)] * d[n];
+        d[m] = t * invd[m];
+    }
+}
 __device__ __forceinline__ bool eliminate(double (&V)[21], const double (&b)[6], double lam,
                                           double (&invd)[6], double (&z)[6]) {
     const bool ok = cholesky6(V, lam, invd);
@@ -1356,13 +1375,7 @@ __device__ __forceinline__ void finish_view_lane(const double (&V)[21], const do
                                                  int v, const int* __restrict__ view_ext, const double* __restrict__ Pc,
                                                  double* __restrict__ Pn, T* __restrict__ VC) {
     double d[6];
-#pragma unroll
-    for (int m = 5; m >= 0; --m) {
-        double t = z[m];
-#pragma unroll
-        for (int n = m + 1; n < 6; ++n) t -= V[tri(n, m)] * d[n];
-        d[m] = t * invd[m];
-    }
+    backward6(V, invd, z, d);
     const int64_t o = L + 6 * (int64_t)view_ext[v];
     double en[6];
 #pragma unroll
@@ -1454,11 +1467,7 @@ __global__ __launch_bounds__(kSchurBlock, (!WIDE && STREAM) ? 3 : 4) void schur_
     const double* G = blockIdx.y ? G1 : G0;
     double V[21], b[6];
     int v0 = blockIdx.x * kSchurViewsPerBlock;
-    if (v0 + grp < nv) {
-        // view_item0 == nullptr: every view is a single item (item index == view index)
-        const int v = v0 + grp, i0 = view_item0 ? view_item0[v] : v;
-        load_view_head<L, WIDE>(G, i0, view_item0 ? view_item0[v + 1] - i0 : 1, (STREAM ? stream_extra_item(sm, v) : -1), c, V, b);
-    }
+    if (v0 + grp < nv) load_view_head<L, WIDE>(G, view_span<STREAM>(view_item0, sm, v0 + grp), c, V, b);
     if (st->done) return;
     const bool boot = st->round == 0;
     const int cand = st->cur ^ 1;
@@ -1480,10 +1489,8 @@ __global__ __launch_bounds__(kSchurBlock, (!WIDE && STREAM) ? 3 : 4) void schur_
         const bool live = v0 + grp < nv;                      // whole 16-lane group together
         const bool more = v0 + stride + grp < nv;
         double rn[6];
-        if (WIDE && more) {                                   // the next trip's seven rows: in flight during this elimination
-            const int v = v0 + stride + grp, i0 = view_item0 ? view_item0[v] : v;
-            request_head_rows(G, i0, view_item0 ? view_item0[v + 1] - i0 : 1, (STREAM ? stream_extra_item(sm, v) : -1), c, rn);
-        }
+        if (WIDE && more)                                     // the next trip's seven rows: in flight during this elimination
+            request_head_rows(G, view_span<STREAM>(view_item0, sm, v0 + stride + grp), c, rn);
         if (live) {
             double invd[6];
             const bool ok = eliminate(V, b, lam, invd, z);
@@ -1498,8 +1505,7 @@ __global__ __launch_bounds__(kSchurBlock, (!WIDE && STREAM) ? 3 : 4) void schur_
             if constexpr (WIDE) {
                 expand_head_rows<L>(rn, c, V, b);
             } else {                                          // the next trip's heads, behind this trip's MFMAs
-                const int v = v0 + grp, i0 = view_item0 ? view_item0[v] : v;
-                load_view_head<L, false>(G, i0, view_item0 ? view_item0[v + 1] - i0 : 1, (STREAM ? stream_extra_item(sm, v) : -1), c, V, b);
+                load_view_head<L, false>(G, view_span<STREAM>(view_item0, sm, v0 + grp), c, V, b);
             }
         }
         // W^T W: K-slot k = this lane's view, six rows per view
@@ -1810,6 +1816,16 @@ __device__ __forceinline__ bool spd_solve_wave0(double (&row)[N + 1], int i, dou
 }
 
 // ---------------------------------------------------------------- update (16 lanes, device function)
+// The accept / reject rule of src/calibrate.py:155-168: round 0 takes the candidate (the bootstrap); later rounds
+// accept it when its error is below the current one -- strict, NaN rejects (:161) -- and divide lambda by 10, or
+// keep the current point and multiply lambda by 10. `cur` indexes the buffers of the point the step starts from.
+struct LMDecision { int cur; double lam; bool acc; };
+__device__ __forceinline__ LMDecision lm_decide(int cur, double lam, int round, double err_cand, double err_cur) {
+    if (round == 0) return {cur ^ 1, lam, false};
+    if (err_cand < err_cur) return {cur ^ 1, lam / 10, true};
+    return {cur, lam * 10, false};
+}
+
 // The control flow of src/calibrate.py:155-168 and the L x L solve S dc = s of the shared block.
 // The LM state is double-buffered per round (in: this round's, out: next round's), so EVERY
 // 16-lane group of the update kernel below can run this redundantly from the same inputs and
@@ -1833,7 +1849,6 @@ __device__ __forceinline__ bool lm_update_step(const LMState* __restrict__ in, L
     }
     double* Pb[2] = {P0, P1};
     int cur = in->cur;
-    const int cand = cur ^ 1;
     const int round = in->round;
     const double err_cand = red[kSse];
     double lam = in->lam;
@@ -1862,24 +1877,24 @@ __device__ __forceinline__ bool lm_update_step(const LMState* __restrict__ in, L
     bool done = false;
     double err_cur_new = err_cand, last_err = err_cand;
     int iters = in->iters, accepted = 0;
-    if (round == 0) {
-        cur = cand;
-    } else {
+    const double err_cur = in->err_cur;
+    const LMDecision dec = lm_decide(cur, lam, round, err_cand, err_cur);
+    if (round > 0) {
         const int it = round - 1;
-        const double err_cur = in->err_cur;
-        const bool acc = err_cand < err_cur;         // strict; NaN rejects (src/calibrate.py:161)
         if (trace && writer) {
             double* row = trace + (int64_t)it * (5 + L);
             if (i < L) row[5 + i] = Pb[cur][i];
-            if (i == 0) { row[0] = it; row[1] = err_cur; row[2] = err_cand; row[3] = lam; row[4] = acc ? 1.0 : 0.0; }
+            if (i == 0) { row[0] = it; row[1] = err_cur; row[2] = err_cand; row[3] = lam; row[4] = dec.acc ? 1.0 : 0.0; }
         }
-        if (acc) { cur = cand; lam = lam / 10; } else { lam = lam * 10; useB = true; }
-        done = !(in->lam_min < lam && lam < in->lam_max) || err_cur < in->err_min || it + 1 >= in->max_iters;
+        useB = !dec.acc;
+        done = !(in->lam_min < dec.lam && dec.lam < in->lam_max) || err_cur < in->err_min || it + 1 >= in->max_iters;
         last_err = err_cur;                          // the reference returns the pre-update error (:155,171)
-        err_cur_new = acc ? err_cand : err_cur;
+        err_cur_new = dec.acc ? err_cand : err_cur;
         iters = it + 1;
-        accepted = acc ? 1 : 0;
+        accepted = dec.acc ? 1 : 0;
     }
+    cur = dec.cur;
+    lam = dec.lam;
     int error = 0;
     if (!done && (useB ? nfailB : nfailA) > 0.0) { error = -3; done = true; }
 
@@ -1940,7 +1955,7 @@ __device__ __forceinline__ bool lm_update_step(const LMState* __restrict__ in, L
 
 // ---------------------------------------------------------------- update + back-substitution + next view constants
 // One launch per LM round after the reduce (and, across GPUs, the all-reduce): every workgroup
-// (a) takes the accept/reject decision and solves for dc (lm_update_step, redundantly, one 16-lane
+// (a) takes the accept/reject decision and solves for dc (decide_and_publish, redundantly, one 16-lane
 // group per workgroup), then every 16-lane group
 // (b) back-substitutes its view, delta_i = Vh^-1 (g_i - E_i^T dc), and writes the view's part of
 // the next candidate P[cur^1] = P[cur] + delta, (c) turns the candidate's Euler angles (degrees)
@@ -1957,15 +1972,8 @@ __device__ __forceinline__ void finish_view(const double (&V)[21], const double 
     double w[6];
 #pragma unroll
     for (int m = 0; m < 6; ++m) w[m] = group_sum16(coef * z[m]);
-    // Lc^T d = w
     double d[6];
-#pragma unroll
-    for (int m = 5; m >= 0; --m) {
-        double t = w[m];
-#pragma unroll
-        for (int n = m + 1; n < 6; ++n) t -= V[tri(n, m)] * d[n];
-        d[m] = t * invd[m];
-    }
+    backward6(V, invd, w, d);
     const int64_t o = L + 6 * (int64_t)view_ext[v];
     double en[6];
 #pragma unroll
@@ -2003,63 +2011,64 @@ __device__ __forceinline__ void finish_view(const double (&V)[21], const double 
     if (c < 2) dst[16 + c] = (T)(c == 0 ? o18[16] : o18[17]);
 }
 
-template <int L, typename T, bool WIDE, bool STREAM>
-// (the narrow-load form holds 27 loaded values beside the solve's rows: 130 registers. At four workgroups per CU it
-// spilled 12-20 bytes per lane; three per CU fit without scratch but turn c4's 782 workgroups into two rounds (12.3 us
-// instead of 10.3). Shards beyond the small kernel's reach therefore load wide by default (calib_lm.hip: wide_heads),
-// which needs 122 registers; this form runs on request only, CALIB_HEAD_LOADS=narrow)
-__global__ __launch_bounds__(kSchurThreads, WIDE ? 4 : 3) void update_backsub_kernel(
-        const double* __restrict__ G0, const double* __restrict__ G1, const LMState* __restrict__ st_in,
-        LMState* __restrict__ st_out, const double* __restrict__ red, const int* __restrict__ view_item0,
-        const int* __restrict__ view_ext, int nv, StreamMap sm, double* __restrict__ P0, double* __restrict__ P1,
-        double* __restrict__ trace, T* __restrict__ VC) {
-    const int tid = threadIdx.x, c = tid & 15;
-    const bool writer = blockIdx.x == 0 && tid < 16;
-    // the first 16-lane group of every workgroup takes the decision and solves; the others get
-    // (go, cur, lambda, dc) through LDS
-    __shared__ double sdec[L + 3];
+// arguments of the three update kernels (filled by calib_lm.hip: launch_update_backsub_t)
+template <typename T>
+struct UpdArgs {
+    const double* G0; const double* G1;    // the round's two record buffers (candidate / current blocks)
+    const LMState* st_in; LMState* st_out; // this round's LM state, the next round's
+    const double* red;                     // the reduce buffer (all ranks' sums)
+    const int* view_item0;                 // first item of each view; null: every view is a single item
+    const int* view_ext;                   // external index of each view
+    int nv;
+    StreamMap sm;
+    double* P0; double* P1;                // parameter buffers: P[cur] current, P[cur ^ 1] the next candidate
+    double* trace;
+    T* VC;                                 // view constants of the next candidate
+};
+
+// The first 16 lanes of a workgroup take the decision and solve (lm_update_step) and publish (go, cur, lambda, dc)
+// in sdec for the rest of the workgroup; lanes c of that group call this, the caller holds the barrier.
+template <int L, typename T>
+__device__ __forceinline__ void decide_and_publish(const UpdArgs<T>& a, int c, double (&sdec)[L + 3]) {
+    const bool writer = blockIdx.x == 0;
     int cur = 0;
     double lam = 0.0, dc[L];
-    if (tid < 16) {
-        const bool go = lm_update_step<L>(st_in, st_out, red, P0, P1, trace, writer, c, cur, lam, dc);
-        if (c == 0) { sdec[0] = go ? 1.0 : 0.0; sdec[1] = (double)cur; sdec[2] = lam; }
-        if (c < L) {
-            double dci = 0.0;
+    const bool go = lm_update_step<L>(a.st_in, a.st_out, a.red, a.P0, a.P1, a.trace, writer, c, cur, lam, dc);
+    if (c == 0) { sdec[0] = go ? 1.0 : 0.0; sdec[1] = (double)cur; sdec[2] = lam; }
+    if (c < L) {
+        double dci = 0.0;
 #pragma unroll
-            for (int j = 0; j < L; ++j) if (j == c) dci = dc[j];
-            sdec[3 + c] = dci;
-        }
+        for (int j = 0; j < L; ++j) if (j == c) dci = dc[j];
+        sdec[3 + c] = dci;
     }
+}
+
+// 16 lanes per view, record heads loaded wide (request_head_rows), the next view's rows in flight during this view's update
+template <int L, typename T, bool STREAM>
+__global__ __launch_bounds__(kSchurThreads, 4) void update_backsub_kernel(UpdArgs<T> a) {
+    const int tid = threadIdx.x, c = tid & 15;
+    __shared__ double sdec[L + 3];
+    if (tid < 16) decide_and_publish<L>(a, c, sdec);
     __syncthreads();
     if (sdec[0] == 0.0) return;
-    cur = (int)sdec[1];
-    lam = sdec[2];
+    const int cur = (int)sdec[1];
+    const double lam = sdec[2];
     const double coef = c < L ? -sdec[3 + c] : (c == L ? 1.0 : 0.0);
-    const double* G = cur ? G1 : G0;
-    const double* Pc = cur ? P1 : P0;
-    double* Pn = cur ? P0 : P1;
+    const double* G = cur ? a.G1 : a.G0;
+    const double* Pc = cur ? a.P1 : a.P0;
+    double* Pn = cur ? a.P0 : a.P1;
     // grid-stride over views: the decision / solve above is paid once per workgroup, not per view
     const int stride = gridDim.x * (kSchurThreads / 16);
     int v = blockIdx.x * (kSchurThreads / 16) + (tid >> 4);
     double rn[6];
-    if (WIDE && v < nv) {
-        const int i0 = view_item0 ? view_item0[v] : v;
-        request_head_rows(G, i0, view_item0 ? view_item0[v + 1] - i0 : 1, (STREAM ? stream_extra_item(sm, v) : -1), c, rn);
-    }
-    for (; v < nv; v += stride) {
+    if (v < a.nv) request_head_rows(G, view_span<STREAM>(a.view_item0, a.sm, v), c, rn);
+    for (; v < a.nv; v += stride) {
         double V[21], b[6], invd[6], z[6];
-        if constexpr (WIDE) {
-            expand_head_rows<L>(rn, c, V, b);
-            if (v + stride < nv) {                            // the next view's rows: in flight during this view's update
-                const int vn = v + stride, i0 = view_item0 ? view_item0[vn] : vn;
-                request_head_rows(G, i0, view_item0 ? view_item0[vn + 1] - i0 : 1, (STREAM ? stream_extra_item(sm, vn) : -1), c, rn);
-            }
-        } else {
-            const int i0 = view_item0 ? view_item0[v] : v;
-            load_view_head<L, false>(G, i0, view_item0 ? view_item0[v + 1] - i0 : 1, (STREAM ? stream_extra_item(sm, v) : -1), c, V, b);
-        }
+        expand_head_rows<L>(rn, c, V, b);
+        if (v + stride < a.nv)                                // the next view's rows: in flight during this view's update
+            request_head_rows(G, view_span<STREAM>(a.view_item0, a.sm, v + stride), c, rn);
         eliminate(V, b, lam, invd, z);
-        finish_view<L, T>(V, invd, z, coef, c, v, view_ext, Pc, Pn, VC);
+        finish_view<L, T>(V, invd, z, coef, c, v, a.view_ext, Pc, Pn, a.VC);
     }
 }
 
@@ -2067,7 +2076,7 @@ __global__ __launch_bounds__(kSchurThreads, WIDE ? 4 : 3) void update_backsub_ke
 // of latencies rather than work: wave 0 of a workgroup is the SOLVER (its first 16 lanes: decision + L x L
 // solve), the other kUpdViewWaves waves own views. The accept / reject decision itself needs two scalars
 // (err(candidate) from the reduce buffer, err(current) from the state), so the view waves take it redundantly
-// and request and eliminate their view's block WHILE the solver works; they meet at the barrier, where dc
+// (lm_decide) and request and eliminate their view's block WHILE the solver works; they meet at the barrier, where dc
 // arrives through LDS. (For large shards the idle solver lanes and the registers of two code paths cost more
 // than the overlap gives: c3 +1.5 us, c5 +12 us; c2 -1.2 us.)
 constexpr int kUpdViewWaves = 4;
@@ -2075,53 +2084,30 @@ constexpr int kUpdThreads = 64 * (1 + kUpdViewWaves);
 constexpr int kUpdViewsPerBlock = kUpdViewWaves * 4;
 
 template <int L, typename T, bool STREAM>
-__global__ __launch_bounds__(kUpdThreads) void update_backsub_small_kernel(
-        const double* __restrict__ G0, const double* __restrict__ G1, const LMState* __restrict__ st_in,
-        LMState* __restrict__ st_out, const double* __restrict__ red, const int* __restrict__ view_item0,
-        const int* __restrict__ view_ext, int nv, StreamMap sm, double* __restrict__ P0, double* __restrict__ P1,
-        double* __restrict__ trace, T* __restrict__ VC) {
+__global__ __launch_bounds__(kUpdThreads) void update_backsub_small_kernel(UpdArgs<T> a) {
     constexpr int kSse = 2 * L * L + 2 * L + 1;
     const int tid = threadIdx.x, c = tid & 15, wave = tid >> 6;
-    const bool writer = blockIdx.x == 0 && tid < 16;
     __shared__ double sdec[L + 3];
     int cur = 0;
     double lam = 0.0;
     double V[21], b[6], invd[6], z[6];
     const int v = blockIdx.x * kUpdViewsPerBlock + ((tid - 64) >> 4);       // one trip: gridDim.x covers the views
     if (wave == 0) {
-        if (tid < 16) {
-            double dc[L];
-            const bool go = lm_update_step<L>(st_in, st_out, red, P0, P1, trace, writer, c, cur, lam, dc);
-            if (c == 0) { sdec[0] = go ? 1.0 : 0.0; sdec[1] = (double)cur; sdec[2] = lam; }
-            if (c < L) {
-                double dci = 0.0;
-#pragma unroll
-                for (int j = 0; j < L; ++j) if (j == c) dci = dc[j];
-                sdec[3 + c] = dci;
-            }
-        }
+        if (tid < 16) decide_and_publish<L>(a, c, sdec);
     } else {
-        // the decision of lm_update_step (src/calibrate.py:155-168), from the same two numbers
-        cur = st_in->cur;
-        lam = st_in->lam;
-        if (st_in->round == 0) {
-            cur ^= 1;
-        } else if (red[kSse] < st_in->err_cur) {
-            cur ^= 1;
-            lam = lam / 10;
-        } else {
-            lam = lam * 10;
-        }
-        if (v < nv) {
-            const int i0 = view_item0 ? view_item0[v] : v;
-            load_view_head<L, false>(cur ? G1 : G0, i0, view_item0 ? view_item0[v + 1] - i0 : 1, (STREAM ? stream_extra_item(sm, v) : -1), c, V, b);
+        const LMState* in = a.st_in;
+        const LMDecision dec = lm_decide(in->cur, in->lam, in->round, a.red[kSse], in->err_cur);
+        cur = dec.cur;
+        lam = dec.lam;
+        if (v < a.nv) {
+            load_view_head<L, false>(cur ? a.G1 : a.G0, view_span<STREAM>(a.view_item0, a.sm, v), c, V, b);
             eliminate(V, b, lam, invd, z);
         }
     }
     __syncthreads();
-    if (sdec[0] == 0.0 || wave == 0 || v >= nv) return;
+    if (sdec[0] == 0.0 || wave == 0 || v >= a.nv) return;
     const double coef = c < L ? -sdec[3 + c] : (c == L ? 1.0 : 0.0);
-    finish_view<L, T>(V, invd, z, coef, c, v, view_ext, cur ? P1 : P0, cur ? P0 : P1, VC);
+    finish_view<L, T>(V, invd, z, coef, c, v, a.view_ext, cur ? a.P1 : a.P0, cur ? a.P0 : a.P1, a.VC);
 }
 
 // The same round step for LARGE shards, one LANE per view (round 4). With 16 lanes per view every group repeats the
@@ -2133,28 +2119,10 @@ __global__ __launch_bounds__(kUpdThreads) void update_backsub_small_kernel(
 // part of the next candidate and the candidate's view constants. ~500 vector instructions per SIXTY-FOUR views.
 // Needs many views to fill the chip (a wave per 64 of them): the host takes it above kUpdLaneViews.
 template <int L, typename T, bool STREAM>
-__global__ __launch_bounds__(kSchurThreads, 3) void update_backsub_lane_kernel(
-        const double* __restrict__ G0, const double* __restrict__ G1, const LMState* __restrict__ st_in,
-        LMState* __restrict__ st_out, const double* __restrict__ red, const int* __restrict__ view_item0,
-        const int* __restrict__ view_ext, int nv, StreamMap sm, double* __restrict__ P0, double* __restrict__ P1,
-        double* __restrict__ trace, T* __restrict__ VC) {
-    const int tid = threadIdx.x, c = tid & 15;
-    const bool writer = blockIdx.x == 0 && tid < 16;
+__global__ __launch_bounds__(kSchurThreads, 3) void update_backsub_lane_kernel(UpdArgs<T> a) {
+    const int tid = threadIdx.x;
     __shared__ double sdec[L + 3];
-    {
-        int cur0 = 0;
-        double lam0 = 0.0, dc0[L];
-        if (tid < 16) {
-            const bool go = lm_update_step<L>(st_in, st_out, red, P0, P1, trace, writer, c, cur0, lam0, dc0);
-            if (c == 0) { sdec[0] = go ? 1.0 : 0.0; sdec[1] = (double)cur0; sdec[2] = lam0; }
-            if (c < L) {
-                double dci = 0.0;
-#pragma unroll
-                for (int j = 0; j < L; ++j) if (j == c) dci = dc0[j];
-                sdec[3 + c] = dci;
-            }
-        }
-    }
+    if (tid < 16) decide_and_publish<L>(a, tid, sdec);
     __syncthreads();
     if (sdec[0] == 0.0) return;
     const int cur = (int)sdec[1];
@@ -2166,10 +2134,10 @@ __global__ __launch_bounds__(kSchurThreads, 3) void update_backsub_lane_kernel(
         dc[j] = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(t)),
                                  __builtin_amdgcn_readfirstlane(__double2loint(t)));
     }
-    const double* G = cur ? G1 : G0;
-    const double* Pc = cur ? P1 : P0;
-    double* Pn = cur ? P0 : P1;
-    for (int v = blockIdx.x * kSchurThreads + tid; v < nv; v += gridDim.x * kSchurThreads) {
+    const double* G = cur ? a.G1 : a.G0;
+    const double* Pc = cur ? a.P1 : a.P0;
+    double* Pn = cur ? a.P0 : a.P1;
+    for (int v = blockIdx.x * kSchurThreads + tid; v < a.nv; v += gridDim.x * kSchurThreads) {
         double V[21], gv[6], acc[6];
 #pragma unroll
         for (int i = 0; i < 21; ++i) V[i] = 0.0;
@@ -2194,17 +2162,14 @@ __global__ __launch_bounds__(kSchurThreads, 3) void update_backsub_lane_kernel(
                 if (m == 1) gv[5] += r[L + 2];
             }
         };
-        const int i0 = view_item0 ? view_item0[v] : v, i1 = view_item0 ? view_item0[v + 1] : v + 1;
-        for (int it = i0; it < i1; ++it) addRecord(G + (int64_t)it * kGStride);
-        if (STREAM) {
-            const int e = stream_extra_item(sm, v);
-            if (e >= 0) addRecord(G + (int64_t)e * kGStride);
-        }
+        const ViewSpan s = view_span<STREAM>(a.view_item0, a.sm, v);
+        for (int it = s.i0; it < s.i0 + s.nitems; ++it) addRecord(G + (int64_t)it * kGStride);
+        if (s.extra >= 0) addRecord(G + (int64_t)s.extra * kGStride);
         double rhs[6], invd[6], z[6];
 #pragma unroll
         for (int m = 0; m < 6; ++m) rhs[m] = gv[m] - acc[m];
         eliminate(V, rhs, lam, invd, z);
-        finish_view_lane<L, T>(V, invd, z, v, view_ext, Pc, Pn, VC);
+        finish_view_lane<L, T>(V, invd, z, v, a.view_ext, Pc, Pn, a.VC);
     }
 }
 
