@@ -842,15 +842,25 @@ __global__ __launch_bounds__(256, CALIB_STREAM_MIN_BLOCKS) void fused_stream_ker
     const unsigned long long tstart = __builtin_amdgcn_s_memtime();
     unsigned long long tlast = tstart;
 #endif
-    if (sel && st->done) return;
-    const double* P = selectP(P0, P1, st, sel);
+    // Nothing waits for the LM state that does not need it. The update kernel wrote st a moment ago; the op table, the
+    // points and the view constants are inputs no launch of the round's tail touches, and the shared parameters can be
+    // requested from BOTH P buffers. So all of those are requested first and the state behind them (readState: its load
+    // travels with theirs instead of ahead of them, as in reduce_kernel), and the finished flag is tested before the
+    // first store to memory: a round enqueued after the end of the refinement still writes nothing.
+    int fin = 0, useP1 = 0;
+    auto readState = [&]() {
+        if (sel) {                                            // sel 0: explicit P0 / G0, the state is not looked at
+            fin = st->done;
+            useP1 = st->cur ^ 1;                              // the candidate's buffers (selectP)
+        }
+    };
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int c = lane & 15, k = lane >> 4;
     const int sl = (lane & 48) | ((lane & 7) << 1) | ((lane >> 3) & 1);
     T2* slab = reinterpret_cast<T2*>(smem) + wave * SLAB;
     double d0u = 0.0, d0v = 0.0, d1u = 0.0, d1v = 0.0, d2u = 0.0;
-    double* Gbase = sel ? ((st->cur ^ 1) ? G1 : G0) : G0;
+    double* Gbase = G0;                                       // chosen with the state, before the first record leaves
     // block results: lane (i, b, j) = (k, bi, bj) holds entry (4 b + i, 4 b' + j) of block (b, b'), b' = b, b + 1, b + 2
     const int bi = (lane >> 2) & 3, bj = lane & 3;
     const int trow = 4 * bi + k, tcol0 = 4 * bi + bj, tcol1 = 4 * ((bi + 1) & 3) + bj, tcol2 = 4 * ((bi + 2) & 3) + bj;
@@ -909,8 +919,10 @@ __global__ __launch_bounds__(256, CALIB_STREAM_MIN_BLOCKS) void fused_stream_ker
         int va = __builtin_amdgcn_readfirstlane(p0 / n);      // the view being accumulated
         int vend = (va + 1) * n;                              // its end = the next boundary, in points
         int slot = p0 != va * n ? nv + w : va;
-        Shared<MODEL, T> sp;
-        sp.load(P);
+        Shared<MODEL, T> sp, spB;                              // spB: the other P buffer's, lives only in the prologue
+        sp.load(P0);
+        spB = sp;
+        if (sel) spB.load(P1);
         // the constant parts of the slab rows (see fused_kernel)
         if (lane < ROWS) {
             T2 c3, c4;
@@ -942,6 +954,10 @@ __global__ __launch_bounds__(256, CALIB_STREAM_MIN_BLOCKS) void fused_stream_ker
         };
         bool strad = straddles(p0, vend);
         if (strad) vc_n = stagedLoad(va); else scalarLoad(va);
+        readState();
+        if (fin) return;                                      // the same for the whole workgroup; nothing has been stored
+        if (useP1) sp = spB;
+        Gbase = useP1 ? G1 : G0;
         const T2* src = slab + rowOff(k);                      // rows 4 s + k: + 66 chunks per group
         const int c1 = (c + 4) & 15, c2 = (c + 8) & 15, jh = (lane >> 3) & 1;
         const T* h0 = reinterpret_cast<const T*>(src + c) + jh;
@@ -1151,6 +1167,9 @@ __global__ __launch_bounds__(256, CALIB_STREAM_MIN_BLOCKS) void fused_stream_ker
         }
         // the share's last view (whole, or cut by the share's end)
         emitView(slot);
+    } else {
+        readState();
+        if (fin) return;
     }
     // the workgroup's partial of B, g_c, sum r^2: every wave parks its block accumulators as the two full symmetric
     // 16 x 16 tiles in its (idle) slab; 112 threads add the four waves' entries through the index table
@@ -1433,7 +1452,6 @@ __global__ __launch_bounds__(kSchurBlock, (!WIDE && STREAM) ? 3 : 4) void schur_
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = tid & 15, grp = tid >> 4, k = lane >> 4;
 
     if (blockIdx.y == 2) {
-        if (st->done) return;
         // thread t of each half-block owns one field of the workgroup partials of B, g_c, sum r^2
         constexpr int NF = L * L + L + 1;
         double* out = part + (int64_t)blockIdx.x * VA;
@@ -1451,6 +1469,8 @@ __global__ __launch_bounds__(kSchurBlock, (!WIDE && STREAM) ? 3 : 4) void schur_
             }
             for (; it < n_bpart; it += step) s0 += src[it * kPartStride];
         }
+        // (these blocks are dispatched last; the finished flag travels with the partials instead of ahead of them)
+        if (st->done) return;
         double* sh = &stile[0][0];
         sh[tid] = (s0 + s1) + (s2 + s3);
         __syncthreads();
@@ -1842,11 +1862,6 @@ __device__ __forceinline__ bool lm_update_step(const LMState* __restrict__ in, L
     constexpr int VA = variantSize(L);
     constexpr int kNfail = 2 * L * L + 2 * L, kSse = kNfail + 1;
     const bool w0 = writer && i == 0;
-    if (in->done) {                                  // keep the finished state visible to later rounds
-        if (writer) for (int j = i; j < (int)(sizeof(LMState) / 8); j += 16)
-            reinterpret_cast<double*>(out)[j] = reinterpret_cast<const double*>(in)[j];
-        return false;
-    }
     double* Pb[2] = {P0, P1};
     int cur = in->cur;
     const int round = in->round;
@@ -1873,6 +1888,13 @@ __device__ __forceinline__ bool lm_update_step(const LMState* __restrict__ in, L
         gS = in->gc[i];
     }
     const double nfailA = red[kNfail], nfailB = red[VA + kNfail];
+    // the finished flag is looked at only now: its load travels with the requests above instead of ahead of them
+    // (a dependent round trip less in front of the solve; what was requested is dropped when the loop is over)
+    if (in->done) {                                  // keep the finished state visible to later rounds
+        if (writer) for (int j = i; j < (int)(sizeof(LMState) / 8); j += 16)
+            reinterpret_cast<double*>(out)[j] = reinterpret_cast<const double*>(in)[j];
+        return false;
+    }
     bool useB = false;                               // the reject variant (current blocks, 10 lambda)
     bool done = false;
     double err_cur_new = err_cand, last_err = err_cand;
