@@ -368,9 +368,9 @@ int launch_fused_t(calib_handle_s* h, const LMState* st, int sel) {
                     (const int*)h->item_n.p, (const int*)h->item_view.p, h->n_items, h->uniform_n, p.ipw, p.fused_wpi,
                     (const uint32_t*)h->emit_tab.p, st, sel, h->G[0].p, h->G[1].p, h->bpart.p);
     };
-    if (p.fused == FusedForm::Tile) launch(fused_kernel<MODEL, T, 32, 4, false, false>);
-    else if (p.fused == FusedForm::TileMulti) launch(fused_kernel<MODEL, T, 32, 4, false, true>);
-    else if constexpr (sizeof(T) == 8) launch(fused_kernel<MODEL, T, 32, 4, true, false>);    // Block44: fp64 only
+    if (p.fused == FusedForm::Tile) launch(fused_kernel<MODEL, T, false, false>);
+    else if (p.fused == FusedForm::TileMulti) launch(fused_kernel<MODEL, T, false, true>);
+    else if constexpr (sizeof(T) == 8) launch(fused_kernel<MODEL, T, true, false>);    // Block44: fp64 only
     h->n_bpart = p.fused_blocks;
     LAUNCHED(h, "fused_kernel");
     return CALIB_OK;
@@ -1474,19 +1474,6 @@ int calib_normal_eq(calib_handle_t h, const double* P, double* out_B, double* ou
     }
     return CALIB_OK;
 }
-
-#ifdef CALIB_STREAM_STAMPS
-// diagnostic build only (tools/diag/): the stamped waves' rows of g_sstamps (kSStampSlots values each), then clears
-int calib_debug_stream_stamps(unsigned long long* out, int max_waves) {
-    std::vector<unsigned long long> hst((size_t)calib::kSStampWaves * calib::kSStampSlots);
-    (void)hipMemcpyFromSymbol(hst.data(), HIP_SYMBOL(calib::g_sstamps), hst.size() * 8);
-    const int nw = std::min(max_waves, calib::kSStampWaves);
-    if (out) std::memcpy(out, hst.data(), (size_t)nw * calib::kSStampSlots * 8);
-    std::fill(hst.begin(), hst.end(), 0ull);
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(calib::g_sstamps), hst.data(), hst.size() * 8);
-    return 0;
-}
-#endif
 
 int calib_distort_points(int model, int64_t n, const double* x_norm, const double* k, double* out_xd) {
     if (n < 0 || (n > 0 && (!x_norm || !out_xd)) || !k) return fail(CALIB_E_INVALID, "null argument");

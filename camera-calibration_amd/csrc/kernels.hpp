@@ -48,7 +48,7 @@ constexpr int kMaxL = 10;
 // col, kEmitZero = "nothing". Fisheye (C = 15): the residual rides in MFMA column 15, so both tiles
 // are plain J^T J with J^T r in row 15 and sum r^2 in the corner. Radial-tangential (C = 16):
 // J's constant columns 3 and 4, (1,0) and (0,1), are replaced by one column of (1,1) -- TU[.][3] =
-// sum Ju, TV[.][3] = sum Jv -- and column 4 carries the residual (see fused_kernel).
+// sum Ju, TV[.][3] = sum Jv -- and column 4 carries the residual (see FusedSlab::ONES).
 // tab[0 .. kGStride) describes the item record, tab[kGStride .. kGStride + kPartStride) the partial.
 constexpr int kEmitZero = 256;
 constexpr int kEmitTile = 264;        // doubles per tile in LDS: 256 + the zero slot, padded
@@ -381,11 +381,125 @@ __global__ __launch_bounds__(256) void gram_kernel(const typename Pair<T>::type*
 // kernel fits 80 VGPRs without a spill -- 6 waves per SIMD instead of 4 at 115 VGPRs: c4 shard 20.4 -> 18.9 us; 8 waves
 // spill and cost 30 %; the several-views-per-wave radtan form needs 94: 5 waves)
 constexpr int kFusedRowChunks = 17;                       // 16 columns + 1 pad chunk (odd => conflict-free)
+constexpr int kFusedRows = 32;                            // points transposed per LDS pass: two passes per 64-point batch
+constexpr int kFusedWaves = 4;                            // waves per workgroup
 
-// ROWS = points transposed per LDS pass (32: two passes per 64-point batch, half the lanes
-// writing each time; 64: one pass, twice the LDS). WAVES = waves per workgroup.
-template <int MODEL, typename T, int ROWS, int WAVES, bool G44, bool MULTI>
-__global__ __launch_bounds__(64 * WAVES, (sizeof(T) == 4 ? (MULTI ? 5 : 6)
+// ---- what fused_kernel and fused_stream_kernel share: the wave's slab and the 4x4x4 block form of the contraction
+// A wave's private LDS slab for storage type T and C Jacobian columns: kFusedRows rows (points) of 16 chunks (columns,
+// one (u, v) pair each). After the main loop the same memory holds the wave's two accumulator tiles.
+template <typename T, int C>
+struct FusedSlab {
+    using T2 = typename Pair<T>::type;
+    static constexpr bool MF32 = sizeof(T) == 4;          // fp32 storage: fp32 MFMA per pass, fp64 across passes
+    static constexpr int RS = kFusedRowChunks, ROWS = kFusedRows, WAVES = kFusedWaves;
+    static constexpr bool RCOL = C < 16;                  // a free 16th MFMA column: J^T r and sum r^2 for free
+    // C == 16 (radial-tangential): columns 3 and 4 of J are the constants (1,0) and (0,1). With the u rows
+    // and the v rows accumulated in separate tiles, column 3 can carry (1,1) -- tile_u[.][3] = sum Ju,
+    // tile_v[.][3] = sum Jv, i.e. what columns 3 and 4 used to give -- and column 4 the residual
+    // (ru, rv): (tile_u + tile_v)[.][4] = J^T r, [4][4] = sum r^2, tile_u[3][4] = sum ru, tile_v[3][4] = sum rv.
+    static constexpr bool ONES = !RCOL;
+    // Row r of a wave's slab starts at chunk rowOff(r). fp32 storage: 16 chunks + 1 pad chunk per row. fp64: 16
+    // chunks per row and one pad chunk per PAIR of rows, so that rows 2 m and 2 m + 1 share their bank phase: the
+    // four 16-lane groups a ds_read_b128 is served in each hold the column sets {0-3, 12-15} of an even and {4-11}
+    // of the odd row of a pair (or the other way round) -- 16 distinct chunk phases exactly when the two rows are
+    // in phase. (With a pad chunk per row every group had one 2-way conflict: 8 LDS cycles per read instead of 4.)
+    // Stores stay conflict-free because a point is not processed by lane = row: see pointOf below.
+    static constexpr int SIZE = MF32 ? ROWS * RS : ROWS * 16 + ROWS / 2;          // chunks per wave
+    static constexpr int BYTES = WAVES * SIZE * (int)sizeof(T2);                  // the workgroup's
+    static_assert(SIZE * sizeof(T2) >= 2 * kEmitTile * 8, "tiles must fit the wave's slab");
+    static __device__ __forceinline__ constexpr int rowOff(int r) { return MF32 ? r * RS : r * 16 + (r >> 1); }
+    // Lane l evaluates point pointOf(l) of its batch and stores that row: inside each 16-lane block lanes 0-7 take the
+    // even rows, lanes 8-15 the odd ones. A ds_write_b128 is served 8 consecutive lanes at a time; their rows
+    // 0, 2, .. 14 (or 1, 3, .. 15) have 8 different bank phases in the fp64 layout above. Rows stay in point order,
+    // so the contraction (which groups rows 4 s .. 4 s + 3) and the handling of the last, partial batch do not care.
+    // (Called by fused_stream_kernel; fused_kernel repeats the expression at its `sl`, for the reason given there.)
+    static __device__ __forceinline__ int pointOf(int lane) {
+        return MF32 ? lane : ((lane & 48) | ((lane & 7) << 1) | ((lane >> 3) & 1));
+    }
+    // the constant columns of the slab rows: d(u,v)/duc = (1,0), d(u,v)/dvc = (0,1); for C == 16
+    // column 3 holds (1,1) and column 4 is rewritten with the residual per batch (ONES, above)
+    static __device__ __forceinline__ void initRows(T2* slab, int lane) {
+        if (lane < ROWS) {
+            T2 c3, c4;
+            c3.x = T(1); c3.y = ONES ? T(1) : T(0);
+            c4.x = T(0); c4.y = T(1);
+            slab[rowOff(lane) + 3] = c3;
+            if (!ONES) slab[rowOff(lane) + 4] = c4;
+            // columns 0, 1, 2 are (xd, 0), (0, yd), (yd, 0): their zero halves are set once, the batches
+            // store only the other 8 bytes
+            T* zr = reinterpret_cast<T*>(slab + rowOff(lane));
+            zr[1] = T(0); zr[2] = T(0); zr[5] = T(0);
+        }
+    }
+    // the two accumulator tiles a wave parks in its dead slab (f64 MFMA C/D layout; kEmitZero: the table's zero entry)
+    static __device__ __forceinline__ double* tileU(T2* slab) { return reinterpret_cast<double*>(slab); }
+    static __device__ __forceinline__ double* tileV(T2* slab) { return tileU(slab) + kEmitTile; }
+    // the workgroup's partial of B, g_c, sum r^2 from the parked tiles of all its waves, in wave order, through the
+    // emit table (after the workgroup's barrier)
+    static __device__ __forceinline__ void writePartial(const unsigned char* smem, const uint32_t* emit_tab, double* part) {
+        if ((int)threadIdx.x < kPartStride) {
+            const uint32_t t = emit_tab[kGStride + threadIdx.x];
+            const double* T0 = reinterpret_cast<const double*>(smem);
+            double o = 0.0;
+#pragma unroll
+            for (int w = 0; w < WAVES; ++w) {
+                const double* TUw = reinterpret_cast<const double*>(reinterpret_cast<const T2*>(T0) + w * SIZE);
+                o += TUw[t & 0xffff] + (TUw + kEmitTile)[t >> 16];
+            }
+            part[(int64_t)blockIdx.x * kPartStride + threadIdx.x] = o;
+        }
+    }
+};
+
+// fp64, 4x4x4 form of the contraction (items of several batches). With every CU issuing it, v_mfma_f64_16x16x4_f64 is
+// held to ~47 TFLOP/s by the chip (tools/ubench/ubench6: 0.54 TFLOP/s per CU on a few CUs, 0.19 on
+// all of them); v_mfma_f64_4x4x4_4b -- four independent 4x4x4 products per instruction -- sustains
+// 76 (ubench8), and J^T J is symmetric. So the 16 x 16 tile is built from 4 x 4 blocks: lane
+// (k, b, x) = (lane >> 4, (lane >> 2) & 3, lane & 3) supplies A = J[point k][4 b + x] and
+// B = J[point k][4 b' + x] and receives D[4 b + k'][4 b' + x] in lane (k', b, x) (layout:
+// tools/ubench/mfma4x4_layout). b' = b gives the four diagonal blocks, b' = b + 1 the blocks (0,1)
+// (1,2) (2,3) (3,0), b' = b + 2 the blocks (0,2) (1,3) and their transposes: every block of the
+// symmetric tile or its transpose. The A operand is the same (u, v) chunk the 16x16x4 form reads
+// (column c = lane & 15 of point k); the B operands are columns c + 4 and c + 8 of the same row.
+// Five instructions per group of 4 points: (b,b) and (b,b+1) for the u rows and for the v rows, and
+// ONE for the (b,b+2) blocks: slots b = 0, 1 take them for the u rows, slots b = 2, 3 -- whose
+// (b,b+2) blocks are the transposes (2,0), (3,1) of the same two -- for the v rows. Its operands are
+// 8-byte reads of the lane's own chunk and of chunk c + 8 at the u or the v half (jh, per lane).
+// 5 x 256 MACs per 4 points instead of 2 x 1024.
+struct BlockAcc {
+    // per row kind (u, v) the diagonal blocks (b, b), the blocks (b, b+1) and the blocks (b, b+2) of the 4 x 4 block grid
+    double d0u = 0.0, d0v = 0.0, d1u = 0.0, d1v = 0.0, d2u = 0.0;
+    // block results: lane (i, b, j) = (k, bi, bj) holds entry (4 b + i, 4 b' + j) of block (b, b'), b' = b, b + 1, b + 2
+    int bi, bj, trow, tcol0, tcol1, tcol2;
+    __device__ __forceinline__ explicit BlockAcc(int lane) {
+        const int k = lane >> 4;
+        bi = (lane >> 2) & 3; bj = lane & 3;
+        trow = 4 * bi + k; tcol0 = 4 * bi + bj; tcol1 = 4 * ((bi + 1) & 3) + bj; tcol2 = 4 * ((bi + 2) & 3) + bj;
+    }
+    // One group of 4 points. The operands stay locals of the two kernels (src, c1, h0, h2: rows 4 s + k of the slab,
+    // chunks c and c + 4, and the u or v half of chunks c and c + 8): read through accessors of a shared struct, the
+    // stream kernel's pipelined passes came out with 56 % more s_waitcnt (303 -> 474).
+    __device__ __forceinline__ void contract(const double2& ja, const double2& jb, double ha, double hc) {
+        d0u = __builtin_amdgcn_mfma_f64_4x4x4f64(ja.x, ja.x, d0u, 0, 0, 0);
+        d0v = __builtin_amdgcn_mfma_f64_4x4x4f64(ja.y, ja.y, d0v, 0, 0, 0);
+        d1u = __builtin_amdgcn_mfma_f64_4x4x4f64(ja.x, jb.x, d1u, 0, 0, 0);
+        d1v = __builtin_amdgcn_mfma_f64_4x4x4f64(ja.y, jb.y, d1v, 0, 0, 0);
+        d2u = __builtin_amdgcn_mfma_f64_4x4x4f64(ha, hc, d2u, 0, 0, 0);
+    }
+    // block results -> the full symmetric 16 x 16 tiles
+    __device__ __forceinline__ void park(double* TU, double* TV) const {
+        TU[trow * 16 + tcol0] = d0u;  TV[trow * 16 + tcol0] = d0v;
+        TU[trow * 16 + tcol1] = d1u;  TV[trow * 16 + tcol1] = d1v;
+        TU[tcol1 * 16 + trow] = d1u;  TV[tcol1 * 16 + trow] = d1v;  // the transposes of the (b, b+1) blocks
+        // (b, b+2): lanes of blocks 0, 1 hold the u rows' (0,2), (1,3), lanes of blocks 2, 3 the v rows' (2,0), (3,1)
+        double* T2nd = bi < 2 ? TU : TV;
+        T2nd[trow * 16 + tcol2] = d2u;
+        T2nd[tcol2 * 16 + trow] = d2u;
+    }
+};
+
+template <int MODEL, typename T, bool G44, bool MULTI>
+__global__ __launch_bounds__(64 * kFusedWaves, (sizeof(T) == 4 ? (MULTI ? 5 : 6)
                                                              : (ModelTraits<MODEL>::C == 16 ? 4 : 3))) void fused_kernel(const double* __restrict__ P0, const double* __restrict__ P1,
                                                     const typename Pair<T>::type* __restrict__ uv,
                                                     const typename Pair<T>::type* __restrict__ XY,
@@ -400,25 +514,10 @@ __global__ __launch_bounds__(64 * WAVES, (sizeof(T) == 4 ? (MULTI ? 5 : 6)
                                                     double* __restrict__ part) {
     using T2 = typename Pair<T>::type;
     constexpr int C = ModelTraits<MODEL>::C;
-    constexpr int RS = kFusedRowChunks;
-    constexpr bool MF32 = sizeof(T) == 4;                  // fp32 storage: fp32 MFMA per pass, fp64 across passes
-    // Row r of a wave's slab starts at chunk rowOff(r). fp32 storage: 16 chunks + 1 pad chunk per row. fp64: 16
-    // chunks per row and one pad chunk per PAIR of rows, so that rows 2 m and 2 m + 1 share their bank phase: the
-    // four 16-lane groups a ds_read_b128 is served in each hold the column sets {0-3, 12-15} of an even and {4-11}
-    // of the odd row of a pair (or the other way round) -- 16 distinct chunk phases exactly when the two rows are
-    // in phase. (With a pad chunk per row every group had one 2-way conflict: 8 LDS cycles per read instead of 4.)
-    // Stores stay conflict-free because a point is not processed by lane = row: see sl below.
-    constexpr int SLAB = MF32 ? ROWS * RS : ROWS * 16 + ROWS / 2;
-    auto rowOff = [](int r) { return MF32 ? r * RS : r * 16 + (r >> 1); };
-    constexpr int HALVES = 64 / ROWS;
-    constexpr bool RCOL = C < 16;                          // a free 16th MFMA column: J^T r and sum r^2 for free
-    // C == 16 (radial-tangential): columns 3 and 4 of J are the constants (1,0) and (0,1). With the u rows
-    // and the v rows accumulated in separate tiles, column 3 can carry (1,1) -- tile_u[.][3] = sum Ju,
-    // tile_v[.][3] = sum Jv, i.e. what columns 3 and 4 used to give -- and column 4 the residual
-    // (ru, rv): (tile_u + tile_v)[.][4] = J^T r, [4][4] = sum r^2, tile_u[3][4] = sum ru, tile_v[3][4] = sum rv.
-    constexpr bool ONES = !RCOL;
-    // one slab per wave; after the main loop the same memory holds the wave's two accumulator tiles
-    __shared__ __attribute__((aligned(16))) unsigned char smem[WAVES * SLAB * sizeof(T2)];
+    using Slab = FusedSlab<T, C>;
+    constexpr int RS = Slab::RS, ROWS = Slab::ROWS, WAVES = Slab::WAVES, SLAB = Slab::SIZE;
+    constexpr bool MF32 = Slab::MF32, RCOL = Slab::RCOL, ONES = Slab::ONES;
+    __shared__ __attribute__((aligned(16))) unsigned char smem[Slab::BYTES];                // one slab per wave
     if (sel && st->done) return;
     const double* P = selectP(P0, P1, st, sel);
     const int lane = threadIdx.x & 63;
@@ -433,16 +532,14 @@ __global__ __launch_bounds__(64 * WAVES, (sizeof(T) == 4 ? (MULTI ? 5 : 6)
     const bool valid = item_first < n_items;
     int item = item_first;
     const int c = lane & 15, k = lane >> 4;
-    // Lane l evaluates point sl(l) of its batch and stores row sl(l): inside each 16-lane block lanes 0-7 take the
-    // even rows, lanes 8-15 the odd ones. A ds_write_b128 is served 8 consecutive lanes at a time; their rows
-    // 0, 2, .. 14 (or 1, 3, .. 15) have 8 different bank phases in the fp64 layout above. Rows stay in point order,
-    // so the contraction (which groups rows 4 s .. 4 s + 3) and the handling of the last, partial batch do not care.
+    // FusedSlab::pointOf(lane), spelled out (keep the two in step): as a call -- forced inline or not, either operand
+    // order -- it reorders the prologue of every fp64 form of this kernel (+1 .. +3 instructions, other registers)
     const int sl = MF32 ? lane : ((lane & 48) | ((lane & 7) << 1) | ((lane >> 3) & 1));
     T2* slab = reinterpret_cast<T2*>(smem) + wave * SLAB;
     d4 acc = {0.0, 0.0, 0.0, 0.0}, acc2 = {0.0, 0.0, 0.0, 0.0};
-    // fp64: the Gram is built from 4x4 blocks by v_mfma_f64_4x4x4_4b (see the contraction below): per row kind
-    // (u, v) the diagonal blocks (b, b), the blocks (b, b+1) and the blocks (b, b+2) of the 4 x 4 block grid
-    double d0u = 0.0, d0v = 0.0, d1u = 0.0, d1v = 0.0, d2u = 0.0;
+    // G44 (fp64 only): the Gram is built from 4x4 blocks by v_mfma_f64_4x4x4_4b instead; unused, and compiled away, in
+    // the tile forms
+    BlockAcc blk(lane);
     double* Gbase = sel ? ((st->cur ^ 1) ? G1 : G0) : G0;
     // One wave per item (tile forms): the item's record goes to HBM straight from the accumulators (lane (k, c) holds
     // rows k + 4 reg -- 4 k + reg behind the fp32 MFMA -- of column c; 16 lanes store 128 contiguous bytes): rows
@@ -481,19 +578,7 @@ __global__ __launch_bounds__(64 * WAVES, (sizeof(T) == 4 ? (MULTI ? 5 : 6)
         const int qend = qbeg + per < n ? qbeg + per : n;
         Shared<MODEL, T> sp;
         sp.load(P);
-        // the constant columns of the slab rows: d(u,v)/duc = (1,0), d(u,v)/dvc = (0,1); for C == 16
-        // column 3 holds (1,1) and column 4 is rewritten with the residual per batch (ONES, above)
-        if (lane < ROWS) {
-            T2 c3, c4;
-            c3.x = T(1); c3.y = ONES ? T(1) : T(0);
-            c4.x = T(0); c4.y = T(1);
-            slab[rowOff(lane) + 3] = c3;
-            if (!ONES) slab[rowOff(lane) + 4] = c4;
-            // columns 0, 1, 2 are (xd, 0), (0, yd), (yd, 0): their zero halves are set once, the batches
-            // store only the other 8 bytes
-            T* zr = reinterpret_cast<T*>(slab + rowOff(lane));
-            zr[1] = T(0); zr[2] = T(0); zr[5] = T(0);
-        }
+        Slab::initRows(slab, lane);
         // inputs of the next batch are requested before the current batch is evaluated
         int64_t pn = pbeg + (qbeg + sl < qend ? qbeg + sl : qend - 1);
         T2 m_n = uv[pn], xy_n = XY[pn];
@@ -526,47 +611,42 @@ __global__ __launch_bounds__(64 * WAVES, (sizeof(T) == 4 ? (MULTI ? 5 : 6)
             // and chunk B in lanes 32-63 (lane l + 32 carries the chunk of lane l's row), register B the same for the
             // rows of pass 1. One full-width store per pair and pass instead of two half-empty ones: 8 instead of
             // 13 / 14 store instructions per pass for 4 vector instructions per pair and batch.
+            // (inline here and in fused_stream_kernel: as a shared helper the swap spills the fp32 forms -- 140 / 124 / 52 /
+            // 20 B of scratch -- and the stores of a pass as one move +12 .. +32 instructions into every tile form)
             constexpr int NCH = C - 5 + 1;                      // columns 5..C-1 and the residual
             T2 ch[NCH];
 #pragma unroll
             for (int i = 0; i < C - 5; ++i) ch[i] = Jc[5 + i];
             ch[NCH - 1] = res;
             auto colOf = [](int i) { return i < C - 5 ? 5 + i : (RCOL ? 15 : 4); };
-            if constexpr (HALVES == 2) {
 #pragma unroll
-                for (int i = 0; i + 1 < NCH; i += 2) {
-                    unsigned a[sizeof(T2) / 4], b[sizeof(T2) / 4];
-                    __builtin_memcpy(a, &ch[i], sizeof(T2));
-                    __builtin_memcpy(b, &ch[i + 1], sizeof(T2));
+            for (int i = 0; i + 1 < NCH; i += 2) {
+                unsigned a[sizeof(T2) / 4], b[sizeof(T2) / 4];
+                __builtin_memcpy(a, &ch[i], sizeof(T2));
+                __builtin_memcpy(b, &ch[i + 1], sizeof(T2));
 #pragma unroll
-                    for (int d = 0; d < (int)(sizeof(T2) / 4); ++d) {
-                        const auto r = __builtin_amdgcn_permlane32_swap(a[d], b[d], false, false);
-                        a[d] = r[0];
-                        b[d] = r[1];
-                    }
-                    __builtin_memcpy(&ch[i], a, sizeof(T2));
-                    __builtin_memcpy(&ch[i + 1], b, sizeof(T2));
+                for (int d = 0; d < (int)(sizeof(T2) / 4); ++d) {
+                    const auto r = __builtin_amdgcn_permlane32_swap(a[d], b[d], false, false);
+                    a[d] = r[0];
+                    b[d] = r[1];
                 }
+                __builtin_memcpy(&ch[i], a, sizeof(T2));
+                __builtin_memcpy(&ch[i + 1], b, sizeof(T2));
             }
 #pragma unroll
-            for (int half = 0; half < HALVES; ++half) {
+            for (int half = 0; half < 2; ++half) {
                 if (q0 + ROWS * half >= qend) break;            // wave-uniform
                 __builtin_amdgcn_wave_barrier();
-                T2* row = slab + rowOff(sl & (ROWS - 1));
-                if (HALVES == 1 || (lane >> 5) == half) {
+                T2* row = slab + Slab::rowOff(sl & (ROWS - 1));
+                if ((lane >> 5) == half) {
                     T* rh = reinterpret_cast<T*>(row);
                     rh[0] = Jc[0].x; rh[3] = Jc[1].y; rh[4] = Jc[2].x;  // the non-zero halves of columns 0, 1, 2
                 }
-                if constexpr (HALVES == 2) {
-                    // pairs: every lane stores -- lanes 0-31 the pair's first chunk, lanes 32-63 its second, both for
-                    // row sl & 31 of this pass; columns 3, 4 are constants, set once above
+                // pairs: every lane stores -- lanes 0-31 the pair's first chunk, lanes 32-63 its second, both for
+                // row sl & 31 of this pass; columns 3, 4 are constants, set once above
 #pragma unroll
-                    for (int i = 0; i + 1 < NCH; i += 2) row[lane < 32 ? colOf(i) : colOf(i + 1)] = ch[i + half];
-                    if ((NCH & 1) && (lane >> 5) == half) row[colOf(NCH - 1)] = ch[NCH - 1];
-                } else {
-#pragma unroll
-                    for (int i = 0; i < NCH; ++i) row[colOf(i)] = ch[i];
-                }
+                for (int i = 0; i + 1 < NCH; i += 2) row[lane < 32 ? colOf(i) : colOf(i + 1)] = ch[i + half];
+                if ((NCH & 1) && (lane >> 5) == half) row[colOf(NCH - 1)] = ch[NCH - 1];
                 __builtin_amdgcn_wave_barrier();
                 const int rows = qend - (q0 + ROWS * half);     // valid points in this pass (may exceed ROWS)
                 if constexpr (MF32) {
@@ -599,7 +679,7 @@ __global__ __launch_bounds__(64 * WAVES, (sizeof(T) == 4 ? (MULTI ? 5 : 6)
                     // fp64, 16x16x4 form (items of a single batch): ONE rolled loop over the pass's complete 4-point
                     // groups, full pass or not, keeps the two accumulator tiles in the same registers all the way
                     const int nfull = rows >= ROWS ? ROWS / 4 : rows >> 2;
-                    const T2* src = slab + rowOff(k) + c;              // rows 4 s + k: + 66 chunks per group
+                    const T2* src = slab + Slab::rowOff(k) + c;        // rows 4 s + k: + 66 chunks per group
                     for (int s = 0; s < nfull; ++s) {
                         const T2 ja = *src;
                         src += 66;
@@ -614,47 +694,26 @@ __global__ __launch_bounds__(64 * WAVES, (sizeof(T) == 4 ? (MULTI ? 5 : 6)
                         acc2 = __builtin_amdgcn_mfma_f64_16x16x4f64(jy, jy, acc2, 0, 0, 0);
                     }
                 } else {
-                    // fp64, 4x4x4 form (items of several batches). With every CU issuing it, v_mfma_f64_16x16x4_f64 is
-                    // held to ~47 TFLOP/s by the chip (tools/ubench/ubench6: 0.54 TFLOP/s per CU on a few CUs, 0.19 on
-                    // all of them); v_mfma_f64_4x4x4_4b -- four independent 4x4x4 products per instruction -- sustains
-                    // 76 (ubench8), and J^T J is symmetric. So the 16 x 16 tile is built from 4 x 4 blocks: lane
-                    // (k, b, x) = (lane >> 4, (lane >> 2) & 3, lane & 3) supplies A = J[point k][4 b + x] and
-                    // B = J[point k][4 b' + x] and receives D[4 b + k'][4 b' + x] in lane (k', b, x) (layout:
-                    // tools/ubench/mfma4x4_layout). b' = b gives the four diagonal blocks, b' = b + 1 the blocks (0,1)
-                    // (1,2) (2,3) (3,0), b' = b + 2 the blocks (0,2) (1,3) and their transposes: every block of the
-                    // symmetric tile or its transpose. The A operand is the same (u, v) chunk the 16x16x4 form reads
-                    // (column c = lane & 15 of point k); the B operands are columns c + 4 and c + 8 of the same row.
-                    // Five instructions per group of 4 points: (b,b) and (b,b+1) for the u rows and for the v rows, and
-                    // ONE for the (b,b+2) blocks: slots b = 0, 1 take them for the u rows, slots b = 2, 3 -- whose
-                    // (b,b+2) blocks are the transposes (2,0), (3,1) of the same two -- for the v rows. Its operands are
-                    // 8-byte reads of the lane's own chunk and of chunk c + 8 at the u or the v half (jh, per lane).
-                    // 5 x 256 MACs per 4 points instead of 2 x 1024.
+                    // fp64, 4x4x4 form (items of several batches): BlockAcc
                     const int nfull = rows >= ROWS ? ROWS / 4 : rows >> 2;
-                    const T2* src = slab + rowOff(k);                  // rows 4 s + k: + 66 chunks per group
+                    const T2* src = slab + Slab::rowOff(k);            // rows 4 s + k: + 66 chunks per group
                     const int c1 = (c + 4) & 15, c2 = (c + 8) & 15, jh = (lane >> 3) & 1;      // jh = 1: blocks 2, 3
                     const T* h0 = reinterpret_cast<const T*>(src + c) + jh;
                     const T* h2 = reinterpret_cast<const T*>(src + c2) + jh;
-                    auto contract = [&](const T2& ja, const T2& jb, double ha, double hc) {
-                        d0u = __builtin_amdgcn_mfma_f64_4x4x4f64((double)ja.x, (double)ja.x, d0u, 0, 0, 0);
-                        d0v = __builtin_amdgcn_mfma_f64_4x4x4f64((double)ja.y, (double)ja.y, d0v, 0, 0, 0);
-                        d1u = __builtin_amdgcn_mfma_f64_4x4x4f64((double)ja.x, (double)jb.x, d1u, 0, 0, 0);
-                        d1v = __builtin_amdgcn_mfma_f64_4x4x4f64((double)ja.y, (double)jb.y, d1v, 0, 0, 0);
-                        d2u = __builtin_amdgcn_mfma_f64_4x4x4f64(ha, hc, d2u, 0, 0, 0);
-                    };
                     if (rows >= ROWS) {
                         // full pass: every address is the wave's constant base plus an immediate
 #pragma unroll
                         for (int s = 0; s < ROWS / 4; ++s)
-                            contract(src[66 * s + c], src[66 * s + c1], (double)h0[2 * 66 * s], (double)h2[2 * 66 * s]);
+                            blk.contract(src[66 * s + c], src[66 * s + c1], h0[2 * 66 * s], h2[2 * 66 * s]);
                     } else {
                         for (int s = 0; s < nfull; ++s)
-                            contract(src[66 * s + c], src[66 * s + c1], (double)h0[2 * 66 * s], (double)h2[2 * 66 * s]);
+                            blk.contract(src[66 * s + c], src[66 * s + c1], h0[2 * 66 * s], h2[2 * 66 * s]);
                         if (rows & 3) {                                 // wave-uniform: the last, incomplete group
                             const bool live = 4 * nfull + k < rows;
                             T2 ja = src[66 * nfull + c], jb = src[66 * nfull + c1];
-                            double ha = (double)h0[2 * 66 * nfull], hc = (double)h2[2 * 66 * nfull];
+                            double ha = h0[2 * 66 * nfull], hc = h2[2 * 66 * nfull];
                             if (!live) { ja.x = T(0); ja.y = T(0); jb.x = T(0); jb.y = T(0); ha = 0.0; hc = 0.0; }
-                            contract(ja, jb, ha, hc);
+                            blk.contract(ja, jb, ha, hc);
                         }
                     }
                 }
@@ -681,9 +740,8 @@ __global__ __launch_bounds__(64 * WAVES, (sizeof(T) == 4 ? (MULTI ? 5 : 6)
     // row = (lane >> 4) + 4 * reg; zeros for a wave without an item) in its dead slab; then the
     // workgroup writes its partial of the shared block and each item's first wave the item's record,
     // both from the index table -- no case analysis, 16-byte coalesced stores.
-    static_assert(SLAB * sizeof(T2) >= 2 * kEmitTile * 8, "tiles must fit the wave's slab");
-    double* TU = reinterpret_cast<double*>(slab);
-    double* TV = TU + kEmitTile;
+    double* TU = Slab::tileU(slab);
+    double* TV = Slab::tileV(slab);
     if (!G44 && wpi == 1 && valid) emitDirect(item);            // the (last) item's record
     __builtin_amdgcn_wave_barrier();                            // the slab is this wave's own: no workgroup barrier needed yet
     if constexpr (!G44) {
@@ -695,30 +753,11 @@ __global__ __launch_bounds__(64 * WAVES, (sizeof(T) == 4 ? (MULTI ? 5 : 6)
             TV[row * 16 + c] = acc2[reg];
         }
     } else {
-        // block results -> the full symmetric 16 x 16 tiles: lane (i, b, j) holds entry (4 b + i, 4 b' + j) of block (b, b')
-        const int bi = (lane >> 2) & 3, j = lane & 3;
-        const int row = 4 * bi + k, col0 = 4 * bi + j, col1 = 4 * ((bi + 1) & 3) + j, col2 = 4 * ((bi + 2) & 3) + j;
-        TU[row * 16 + col0] = d0u;  TV[row * 16 + col0] = d0v;
-        TU[row * 16 + col1] = d1u;  TV[row * 16 + col1] = d1v;
-        TU[col1 * 16 + row] = d1u;  TV[col1 * 16 + row] = d1v;  // the transposes of the (b, b+1) blocks
-        // (b, b+2): lanes of blocks 0, 1 hold the u rows' (0,2), (1,3), lanes of blocks 2, 3 the v rows' (2,0), (3,1)
-        double* T2nd = bi < 2 ? TU : TV;
-        T2nd[row * 16 + col2] = d2u;
-        T2nd[col2 * 16 + row] = d2u;
+        blk.park(TU, TV);
     }
     if (lane == 0) { TU[kEmitZero] = 0.0; TV[kEmitZero] = 0.0; }
     __syncthreads();
-    if ((int)threadIdx.x < kPartStride) {                       // partial of B, g_c, sum r^2: all waves, wave order
-        const uint32_t t = emit_tab[kGStride + threadIdx.x];
-        const double* T0 = reinterpret_cast<const double*>(smem);
-        double o = 0.0;
-#pragma unroll
-        for (int w = 0; w < WAVES; ++w) {
-            const double* TUw = reinterpret_cast<const double*>(reinterpret_cast<const T2*>(T0) + w * SLAB);
-            o += TUw[t & 0xffff] + (TUw + kEmitTile)[t >> 16];
-        }
-        part[(int64_t)blockIdx.x * kPartStride + threadIdx.x] = o;
-    }
+    Slab::writePartial(smem, emit_tab, part);
     if ((!G44 && wpi == 1) || sub != 0 || !valid) return;       // the item's first wave assembles the record from the parked tiles
     double* G = Gbase + (int64_t)item * kGStride;
     if (lane < kGStride / 2) {
@@ -737,14 +776,6 @@ __global__ __launch_bounds__(64 * WAVES, (sizeof(T) == 4 ? (MULTI ? 5 : 6)
     }
 }
 
-#ifdef CALIB_STREAM_STAMPS
-// diagnostic build only (tools/diag/build_stream_stamps.sh): per-wave s_memtime deltas of fused_stream_kernel's phases
-constexpr int kSStampWaves = 8192, kSStampSlots = 16;
-__device__ unsigned long long g_sstamps[kSStampWaves * kSStampSlots];
-#define SSTAMP(i) do { __builtin_amdgcn_s_waitcnt(0xC07F); __builtin_amdgcn_sched_barrier(0); const unsigned long long t__ = __builtin_amdgcn_s_memtime(); tacc[i] += t__ - tlast; tlast = t__; __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define SSTAMP(i) do {} while (0)
-#endif
 // ---------------------------------------------------------------- fused jacobian + gram, stream form
 // The block-form fused kernel for uniform fp64 shards (every view n points, n a multiple of 4 and >= 64), with the
 // per-view fixed cost and the dead lanes of a view's last batch taken out. The shard is ONE stream of 4-point
@@ -767,11 +798,13 @@ __device__ unsigned long long g_sstamps[kSStampWaves * kSStampSlots];
 //    view its share starts in the middle of goes to its overflow slot nv + w (StreamMap / stream_extra_item:
 //    the per-view kernels add the two). Only the entries the per-view kernels read are written: rows L..L+5 of
 //    J^T J and the view's six entries of J^T r (the record buffers are zeroed when they are allocated).
-// Everything else -- slab layout, chunk pairs, the five 4x4x4 instructions per group -- is fused_kernel's G44 form.
+// Everything else is fused_kernel's G44 form: slab layout and workgroup partial from FusedSlab, the five 4x4x4 instructions
+// per group and the tile parking from BlockAcc; the chunk pairs, a pass's slab stores and a group's operand addresses
+// repeat that kernel's text.
 constexpr int kStreamOps = 12;       // byte offsets into the record per lane; kStreamNoOp (past the record) = nothing
 constexpr int kStreamNoOp = 0x7ffffff0;
 // op -> what is stored: 0, 1: d0u + d0v   2, 3: d1u + d1v   4, 5: d2 + the partner lane's d2
-//                       6: d0u  7: d0v  8: d1u  9: d1v  10: d2   (radial-tangential: the (1,1) column, see fused_kernel)
+//                       6: d0u  7: d0v  8: d1u  9: d1v  10: d2   (radial-tangential: the (1,1) column, see FusedSlab::ONES)
 inline bool buildStreamOps(int C, int32_t* ops /* 64 * kStreamOps */) {
     uint32_t tab[kEmitTabSize];
     buildEmitTable(C, tab);
@@ -813,11 +846,9 @@ inline bool buildStreamOps(int C, int32_t* ops /* 64 * kStreamOps */) {
     return ok;
 }
 
-#ifndef CALIB_STREAM_MIN_BLOCKS
-#define CALIB_STREAM_MIN_BLOCKS 4       // workgroups per CU the register allocation leaves room for (A/B builds: 3, 5)
-#endif
+constexpr int kStreamMinBlocks = 4;  // workgroups per CU the register allocation leaves room for: makePlan's wave slots
 template <int MODEL>
-__global__ __launch_bounds__(256, CALIB_STREAM_MIN_BLOCKS) void fused_stream_kernel(const double* __restrict__ P0, const double* __restrict__ P1,
+__global__ __launch_bounds__(64 * kFusedWaves, kStreamMinBlocks) void fused_stream_kernel(const double* __restrict__ P0, const double* __restrict__ P1,
                                                               const double2* __restrict__ uv, const double2* __restrict__ XY,
                                                               const double* __restrict__ Z, const double* __restrict__ VC,
                                                               int n, int nv, int share,
@@ -829,19 +860,12 @@ __global__ __launch_bounds__(256, CALIB_STREAM_MIN_BLOCKS) void fused_stream_ker
     using T = double;
     using T2 = double2;
     constexpr int C = ModelTraits<MODEL>::C, L = C - 6;
-    constexpr int ROWS = 32, WAVES = 4;
-    constexpr int SLAB = ROWS * 16 + ROWS / 2;
-    constexpr bool RCOL = C < 16, ONES = !RCOL;
-    auto rowOff = [](int r) { return r * 16 + (r >> 1); };
-    __shared__ __attribute__((aligned(16))) unsigned char smem[WAVES * SLAB * sizeof(T2)];
+    using Slab = FusedSlab<T, C>;
+    constexpr int ROWS = Slab::ROWS, WAVES = Slab::WAVES, SLAB = Slab::SIZE;
+    constexpr bool RCOL = Slab::RCOL, ONES = Slab::ONES;
+    __shared__ __attribute__((aligned(16))) unsigned char smem[Slab::BYTES];
     __shared__ __attribute__((aligned(16))) double svc[WAVES][2 * kViewStride];
     __shared__ __attribute__((aligned(16))) int32_t sops[64 * kStreamOps];
-    static_assert(SLAB * sizeof(T2) >= 2 * kEmitTile * 8, "tiles must fit the wave's slab");
-#ifdef CALIB_STREAM_STAMPS
-    unsigned long long tacc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const unsigned long long tstart = __builtin_amdgcn_s_memtime();
-    unsigned long long tlast = tstart;
-#endif
     // Nothing waits for the LM state that does not need it. The update kernel wrote st a moment ago; the op table, the
     // points and the view constants are inputs no launch of the round's tail touches, and the shared parameters can be
     // requested from BOTH P buffers. So all of those are requested first and the state behind them (readState: its load
@@ -856,24 +880,21 @@ __global__ __launch_bounds__(256, CALIB_STREAM_MIN_BLOCKS) void fused_stream_ker
     };
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int c = lane & 15, k = lane >> 4;
-    const int sl = (lane & 48) | ((lane & 7) << 1) | ((lane >> 3) & 1);
+    const int k = lane >> 4;
+    const int sl = Slab::pointOf(lane);
     T2* slab = reinterpret_cast<T2*>(smem) + wave * SLAB;
-    double d0u = 0.0, d0v = 0.0, d1u = 0.0, d1v = 0.0, d2u = 0.0;
+    BlockAcc blk(lane);
     double* Gbase = G0;                                       // chosen with the state, before the first record leaves
-    // block results: lane (i, b, j) = (k, bi, bj) holds entry (4 b + i, 4 b' + j) of block (b, b'), b' = b, b + 1, b + 2
-    const int bi = (lane >> 2) & 3, bj = lane & 3;
-    const int trow = 4 * bi + k, tcol0 = 4 * bi + bj, tcol1 = 4 * ((bi + 1) & 3) + bj, tcol2 = 4 * ((bi + 2) & 3) + bj;
     auto ofView = [](int i) { return i >= L && i < L + 6; };
-    const bool keep0 = !(ofView(trow) || ofView(tcol0)), keep1 = !(ofView(trow) || ofView(tcol1)),
-               keep2 = !(ofView(trow) || ofView(tcol2));
+    const bool keep0 = !(ofView(blk.trow) || ofView(blk.tcol0)), keep1 = !(ofView(blk.trow) || ofView(blk.tcol1)),
+               keep2 = !(ofView(blk.trow) || ofView(blk.tcol2));
     // every wave writes the (same) whole table and every lane only ever reads back its own 24 bytes: no barrier
     {
         const int4* src = reinterpret_cast<const int4*>(stream_ops) + 3 * lane;
         int4* dst = reinterpret_cast<int4*>(sops) + 3 * lane;
         dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2];
     }
-    const int partner = bj * 16 + ((bi + 2) & 3) * 4 + k;       // holds the other rows' sums of this lane's (b, b+2) entry
+    const int partner = blk.bj * 16 + ((blk.bi + 2) & 3) * 4 + k;       // holds the other rows' sums of this lane's (b, b+2) entry
     // the finished view's record, straight from the accumulators; then what belongs to a view restarts from zero
     // Every op is ONE buffer store with the lane's byte offset in the voffset: the record is a 1 KiB buffer resource, and
     // an offset past it (kStreamNoOp: "this lane has nothing for this op") is dropped by the hardware's range check -- no
@@ -889,6 +910,7 @@ __global__ __launch_bounds__(256, CALIB_STREAM_MIN_BLOCKS) void fused_stream_ker
         const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(G, 0, kGStride * 8, 0x00020000);
         const int4* o4 = reinterpret_cast<const int4*>(sops) + 3 * lane;
         const int4 oa = o4[0], ob = o4[1];
+        double &d0u = blk.d0u, &d0v = blk.d0v, &d1u = blk.d1u, &d1v = blk.d1v, &d2u = blk.d2u;
         const double s0 = d0u + d0v, s1 = d1u + d1v;
         const double dp = __hiloint2double(__builtin_amdgcn_ds_bpermute(partner << 2, __double2hiint(d2u)),
                                            __builtin_amdgcn_ds_bpermute(partner << 2, __double2loint(d2u)));
@@ -923,16 +945,7 @@ __global__ __launch_bounds__(256, CALIB_STREAM_MIN_BLOCKS) void fused_stream_ker
         sp.load(P0);
         spB = sp;
         if (sel) spB.load(P1);
-        // the constant parts of the slab rows (see fused_kernel)
-        if (lane < ROWS) {
-            T2 c3, c4;
-            c3.x = T(1); c3.y = ONES ? T(1) : T(0);
-            c4.x = T(0); c4.y = T(1);
-            slab[rowOff(lane) + 3] = c3;
-            if (!ONES) slab[rowOff(lane) + 4] = c4;
-            T* zr = reinterpret_cast<T*>(slab + rowOff(lane));
-            zr[1] = T(0); zr[2] = T(0); zr[5] = T(0);
-        }
+        Slab::initRows(slab, lane);
         int pn = p0 + sl < p1 ? p0 + sl : p1 - 1;
         T2 m_n = uv[pn], xy_n = XY[pn];
         T z_n = Z[pn];
@@ -958,19 +971,11 @@ __global__ __launch_bounds__(256, CALIB_STREAM_MIN_BLOCKS) void fused_stream_ker
         if (fin) return;                                      // the same for the whole workgroup; nothing has been stored
         if (useP1) sp = spB;
         Gbase = useP1 ? G1 : G0;
-        const T2* src = slab + rowOff(k);                      // rows 4 s + k: + 66 chunks per group
-        const int c1 = (c + 4) & 15, c2 = (c + 8) & 15, jh = (lane >> 3) & 1;
+        const T2* src = slab + Slab::rowOff(k);                // rows 4 s + k: + 66 chunks per group
+        const int c = lane & 15, c1 = (c + 4) & 15, c2 = (c + 8) & 15, jh = (lane >> 3) & 1;
         const T* h0 = reinterpret_cast<const T*>(src + c) + jh;
         const T* h2 = reinterpret_cast<const T*>(src + c2) + jh;
-        auto contract = [&](const T2& ja, const T2& jb, double ha, double hc) {
-            d0u = __builtin_amdgcn_mfma_f64_4x4x4f64(ja.x, ja.x, d0u, 0, 0, 0);
-            d0v = __builtin_amdgcn_mfma_f64_4x4x4f64(ja.y, ja.y, d0v, 0, 0, 0);
-            d1u = __builtin_amdgcn_mfma_f64_4x4x4f64(ja.x, jb.x, d1u, 0, 0, 0);
-            d1v = __builtin_amdgcn_mfma_f64_4x4x4f64(ja.y, jb.y, d1v, 0, 0, 0);
-            d2u = __builtin_amdgcn_mfma_f64_4x4x4f64(ha, hc, d2u, 0, 0, 0);
-        };
         PointState<MODEL, T> pst;
-        SSTAMP(0);
         for (int q0 = p0; q0 < p1; q0 += 64) {
             const int qe = q0 + 64 < p1 ? q0 + 64 : p1;
             const int q = q0 + sl;
@@ -987,15 +992,7 @@ __global__ __launch_bounds__(256, CALIB_STREAM_MIN_BLOCKS) void fused_stream_ker
                 pn = q + 64 < p1 ? q + 64 : p1 - 1;
                 m_n = uv[pn]; xy_n = XY[pn]; z_n = Z[pn];
                 if (strad2) vc_n = stagedLoad(va2);
-#ifdef CALIB_STREAM_STAMPS
-                __builtin_amdgcn_s_waitcnt(0x0F74);     // vmcnt(4): this batch's points have arrived
-#endif
-            } else {
-#ifdef CALIB_STREAM_STAMPS
-                __builtin_amdgcn_s_waitcnt(0x0F70);
-#endif
             }
-            SSTAMP(1);
             T u, v;
             T2 Jc[C];
             if (!strad) {
@@ -1021,14 +1018,11 @@ __global__ __launch_bounds__(256, CALIB_STREAM_MIN_BLOCKS) void fused_stream_ker
             T2 res;
             res.x = m.x - u;
             res.y = m.y - v;
-#ifdef CALIB_STREAM_STAMPS
-            asm volatile("" :: "v"(res.x), "v"(res.y), "v"(Jc[C - 1].x), "v"(Jc[C - 1].y));
-            if (strad) SSTAMP(3); else SSTAMP(2);
-#endif
             // the SGPRs of the view constants are free now: the next one-view batch's arrive during the contraction
             if (more && !strad2) scalarLoad(vfirst2);
             strad = strad2;
-            // chunk pairs through v_permlane32_swap: one full-width store per pair and pass (see fused_kernel)
+            // chunk pairs through v_permlane32_swap: one full-width store per pair and pass (see fused_kernel, whose text
+            // this repeats: a shared helper spills that kernel's fp32 forms, and the pass's stores need ch[] next to them)
             constexpr int NCH = C - 5 + 1;                      // columns 5..C-1 and the residual
             T2 ch[NCH];
 #pragma unroll
@@ -1054,7 +1048,7 @@ __global__ __launch_bounds__(256, CALIB_STREAM_MIN_BLOCKS) void fused_stream_ker
                 const int ps = q0 + ROWS * half;                // first point of the pass
                 if (ps >= p1) break;                            // wave-uniform
                 __builtin_amdgcn_wave_barrier();
-                T2* row = slab + rowOff(sl & (ROWS - 1));
+                T2* row = slab + Slab::rowOff(sl & (ROWS - 1));
                 if ((lane >> 5) == half) {
                     T* rh = reinterpret_cast<T*>(row);
                     rh[0] = Jc[0].x; rh[3] = Jc[1].y; rh[4] = Jc[2].x;  // the non-zero halves of columns 0, 1, 2
@@ -1063,7 +1057,6 @@ __global__ __launch_bounds__(256, CALIB_STREAM_MIN_BLOCKS) void fused_stream_ker
                 for (int i = 0; i + 1 < NCH; i += 2) row[lane < 32 ? colOf(i) : colOf(i + 1)] = ch[i + half];
                 if ((NCH & 1) && (lane >> 5) == half) row[colOf(NCH - 1)] = ch[NCH - 1];
                 __builtin_amdgcn_wave_barrier();
-                SSTAMP(4);
                 const int ng = (p1 - ps >= ROWS ? ROWS : p1 - ps) >> 2;   // groups of the pass (shares are whole groups)
                 const int jb = (vend - ps) >> 2;                // the group a new view starts with (>= ng: none here)
                 // groups [FROM, TO) of the pass, FROM and TO known at compile time: every address is the wave's constant base
@@ -1082,7 +1075,7 @@ __global__ __launch_bounds__(256, CALIB_STREAM_MIN_BLOCKS) void fused_stream_ker
                                 nha = h0[2 * 66 * (s + 1)]; nhc = h2[2 * 66 * (s + 1)];
                             }
                             __builtin_amdgcn_sched_barrier(0);
-                            contract(ja, jbb, ha, hc);
+                            blk.contract(ja, jbb, ha, hc);
                             __builtin_amdgcn_sched_barrier(0);
                             ja = na; jbb = nb; ha = nha; hc = nhc;
                         }
@@ -1099,10 +1092,6 @@ __global__ __launch_bounds__(256, CALIB_STREAM_MIN_BLOCKS) void fused_stream_ker
                 if (ng == NG && jb >= NG) {
                     // a whole pass inside one view
                     runFixed(integral_constant<int, 0>{}, integral_constant<int, NG>{});
-#ifdef CALIB_STREAM_STAMPS
-                    asm volatile("" :: "v"(d0u), "v"(d0v), "v"(d1u), "v"(d1v), "v"(d2u));
-#endif
-                    SSTAMP(5);
                 } else if (ng == NG) {
                     // a whole pass with a view boundary before group jb: one straight-line copy of the pass per position of
                     // the boundary -- groups [0, jb), the finished view's record, groups [jb, 8) -- so that each run keeps
@@ -1114,17 +1103,8 @@ __global__ __launch_bounds__(256, CALIB_STREAM_MIN_BLOCKS) void fused_stream_ker
                     auto boundaryAt = [&](auto JBc) {
                         constexpr int JB = decltype(JBc)::value;
                         runFixed(integral_constant<int, 0>{}, integral_constant<int, JB>{});
-#ifdef CALIB_STREAM_STAMPS
-                        asm volatile("" :: "v"(d0u), "v"(d0v), "v"(d1u), "v"(d1v), "v"(d2u));
-#endif
-                        SSTAMP(6);
                         nextView();
-                        SSTAMP(7);
                         runFixed(integral_constant<int, JB>{}, integral_constant<int, NG>{});
-#ifdef CALIB_STREAM_STAMPS
-                        asm volatile("" :: "v"(d0u), "v"(d0v), "v"(d1u), "v"(d1v), "v"(d2u));
-#endif
-                        SSTAMP(6);
                     };
                     switch (jb) {
                     case 0: boundaryAt(integral_constant<int, 0>{}); break;
@@ -1141,7 +1121,7 @@ __global__ __launch_bounds__(256, CALIB_STREAM_MIN_BLOCKS) void fused_stream_ker
                     const int sb = jb < ng ? jb : ng;
                     auto runGroups = [&](int from, int to) {
                         switch (from) {
-#define CALIB_GROUP_CASE(S) case S: if (to <= S) break; contract(src[66 * S + c], src[66 * S + c1], h0[2 * 66 * S], h2[2 * 66 * S]); [[fallthrough]];
+#define CALIB_GROUP_CASE(S) case S: if (to <= S) break; blk.contract(src[66 * S + c], src[66 * S + c1], h0[2 * 66 * S], h2[2 * 66 * S]); [[fallthrough]];
                         CALIB_GROUP_CASE(0) CALIB_GROUP_CASE(1) CALIB_GROUP_CASE(2) CALIB_GROUP_CASE(3)
                         CALIB_GROUP_CASE(4) CALIB_GROUP_CASE(5) CALIB_GROUP_CASE(6) CALIB_GROUP_CASE(7)
 #undef CALIB_GROUP_CASE
@@ -1149,18 +1129,9 @@ __global__ __launch_bounds__(256, CALIB_STREAM_MIN_BLOCKS) void fused_stream_ker
                         }
                     };
                     runGroups(0, sb);
-#ifdef CALIB_STREAM_STAMPS
-                    asm volatile("" :: "v"(d0u), "v"(d0v), "v"(d1u), "v"(d1v), "v"(d2u));
-#endif
-                    SSTAMP(6);
                     if (jb < ng) {
                         nextView();
-                        SSTAMP(7);
                         runGroups(sb, ng);
-#ifdef CALIB_STREAM_STAMPS
-                        asm volatile("" :: "v"(d0u), "v"(d0v), "v"(d1u), "v"(d1v), "v"(d2u));
-#endif
-                        SSTAMP(6);
                     }
                 }
             }
@@ -1174,39 +1145,14 @@ __global__ __launch_bounds__(256, CALIB_STREAM_MIN_BLOCKS) void fused_stream_ker
     // the workgroup's partial of B, g_c, sum r^2: every wave parks its block accumulators as the two full symmetric
     // 16 x 16 tiles in its (idle) slab; 112 threads add the four waves' entries through the index table
     {
-        double* TU = reinterpret_cast<double*>(slab);
-        double* TV = TU + kEmitTile;
+        double* TU = Slab::tileU(slab);
+        double* TV = Slab::tileV(slab);
         __builtin_amdgcn_wave_barrier();
-        TU[trow * 16 + tcol0] = d0u;  TV[trow * 16 + tcol0] = d0v;
-        TU[trow * 16 + tcol1] = d1u;  TV[trow * 16 + tcol1] = d1v;
-        TU[tcol1 * 16 + trow] = d1u;  TV[tcol1 * 16 + trow] = d1v;
-        double* T2nd = bi < 2 ? TU : TV;
-        T2nd[trow * 16 + tcol2] = d2u;
-        T2nd[tcol2 * 16 + trow] = d2u;
+        blk.park(TU, TV);
         if (lane == 0) { TU[kEmitZero] = 0.0; TV[kEmitZero] = 0.0; }
     }
-    SSTAMP(8);
     __syncthreads();
-    SSTAMP(9);
-    if ((int)threadIdx.x < kPartStride) {
-        const uint32_t t = emit_tab[kGStride + threadIdx.x];
-        const double* T0 = reinterpret_cast<const double*>(smem);
-        double o = 0.0;
-#pragma unroll
-        for (int wv = 0; wv < WAVES; ++wv) {
-            const double* TUw = reinterpret_cast<const double*>(reinterpret_cast<const T2*>(T0) + wv * SLAB);
-            o += TUw[t & 0xffff] + (TUw + kEmitTile)[t >> 16];
-        }
-        part[(int64_t)blockIdx.x * kPartStride + threadIdx.x] = o;
-    }
-#ifdef CALIB_STREAM_STAMPS
-    SSTAMP(10);
-    if (lane == 0 && w < kSStampWaves) {
-        unsigned long long* o = g_sstamps + (size_t)w * kSStampSlots;
-        for (int i = 0; i < 12; ++i) o[i] = tacc[i];
-        o[12] = tstart; o[13] = tlast; o[14] = 1;
-    }
-#endif
+    Slab::writePartial(smem, emit_tab, part);
 }
 
 // ---------------------------------------------------------------- stream form: which records make up a view

@@ -112,7 +112,7 @@ inline LaunchPlan makePlan(const ShardShape& s, int dtype, int lm_mode, const Kn
     const int un = s.uniform_n;
     const bool can = dtype == CALIB_DTYPE_F64 && un >= 64 && (un & 3) == 0 && s.MN < ((int64_t)1 << 31) && s.nv >= 1;
     if (lm_mode == CALIB_LM_FUSED && can && k.stream_mode != 0) {
-        const int slots = k.stream_waves > 0 ? k.stream_waves : 4 * CALIB_STREAM_MIN_BLOCKS * num_cus;
+        const int slots = k.stream_waves > 0 ? k.stream_waves : kFusedWaves * kStreamMinBlocks * num_cus;
         const int waves = std::max(1, std::min(slots, s.nv));
         if (k.stream_mode == 1 || s.nv >= 2 * slots) {
             const int64_t groups = (int64_t)s.nv * (un / 4);

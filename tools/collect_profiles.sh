@@ -13,7 +13,6 @@ cp $PROFILE_OUT/prof/rehearsal_n2.json profiles/${rnd}_rehearsal_n2_gloo_one_gpu
 cp $PROFILE_OUT/prof/rehearsal_n4.json profiles/${rnd}_rehearsal_n4_gloo_one_gpu.json
 for n in 2 4; do [ -f $PROFILE_OUT/prof/rehearsal_n${n}_direct.json ] && cp $PROFILE_OUT/prof/rehearsal_n${n}_direct.json profiles/${rnd}_rehearsal_n${n}_direct.json; done
 cp $PROFILE_OUT/prof/ubench.txt profiles/${rnd}_ubench.txt
-cp $PROFILE_OUT/prof/stream_stamps.txt profiles/${rnd}_stream_stamps.txt
 # 64-lane batches per fused launch: derived from the launch shape the profiled build reported (config.fused_form in the bench line)
 python3 tools/make_pmc_fused.py --round $rnd --workload c3 --tag c3 --model fisheye > /dev/null
 python3 tools/make_pmc_fused.py --round $rnd --workload c5 --tag c5 --model radtan > /dev/null

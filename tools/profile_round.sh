@@ -58,8 +58,3 @@ for u in ubench6 ubench7 ubench8 ubench10 mfma4x4_layout; do
   [ -x tools/ubench/$u ] && { echo "== $u"; tools/ubench/$u; } >> $PROFILE_OUT/prof/ubench.txt 2>&1
 done
 echo "ubench done"
-# per-phase stamps of the stream kernel (diagnostic build: bash tools/diag/build_stream_stamps.sh first)
-if [ -f tools/diag/lib/stream_stamps/libcalib_lm.so ]; then
-  { python3 tools/diag/stream_stamps.py c3; python3 tools/diag/stream_stamps.py c5 125000; } 2>&1 | grep -vE "amdgpu.ids" > $PROFILE_OUT/prof/stream_stamps.txt
-  echo "stream stamps done"
-fi
