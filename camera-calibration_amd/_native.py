@@ -37,6 +37,8 @@ SIGNATURES = {
     "calib_set_lm_mode": (ctypes.c_int, [_h, ctypes.c_int]),
     "calib_fused_form": (ctypes.c_int, [_h, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "calib_num_shared": (ctypes.c_int, [_h, _c_int_p]),
+    "calib_set_fixed_shared": (ctypes.c_int, [_h, ctypes.c_uint32]),
+    "calib_get_fixed_shared": (ctypes.c_int, [_h, ctypes.POINTER(ctypes.c_uint32)]),
     "calib_num_params": (ctypes.c_int, [_h, _c_int64_p]),
     "calib_eval": (ctypes.c_int, [_h, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
     "calib_normal_eq": (ctypes.c_int, [_h, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
@@ -66,6 +68,9 @@ SIGNATURES = {
                                                      _c_double_p, _c_double_p]),
     "calib_refine_homographies": (ctypes.c_int, [ctypes.c_int64, _c_int64_p, _c_double_p, _c_double_p, _c_double_p,
                                                  ctypes.c_int, ctypes.c_int]),
+    "calib_refine_poses": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, _c_int64_p, _c_double_p, _c_double_p, _c_double_p,
+                                          _c_double_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                          ctypes.c_double, _c_double_p, _c_int_p, _c_int_p, ctypes.c_int]),
     "calib_homography_jacobian": (ctypes.c_int, [ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p, ctypes.c_int]),
     "calib_estimate_homographies": (ctypes.c_int, [ctypes.c_int64, _c_int64_p, _c_double_p, _c_double_p, _c_double_p,
                                                    ctypes.c_int, ctypes.c_int]),

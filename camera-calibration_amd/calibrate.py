@@ -13,6 +13,7 @@ import numpy as np
 
 from . import distortion
 from . import engine
+from . import fixed as fixedmod
 from . import jacobian
 from . import mathutils as mu
 
@@ -23,8 +24,9 @@ class Calibrator:
     _λmax = engine.LAMBDA_MAX
     _Pt_error_min = engine.PT_ERROR_MIN
 
-    def __init__(self, distortionModel: distortion.DistortionModel, *, dtype="f64", device=0):
+    def __init__(self, distortionModel: distortion.DistortionModel, *, fixed=(), dtype="f64", device=0):
         self._distortionModel = distortionModel
+        self.setFixed(fixed)
         self._jac = None
         self._dtype = dtype
         self._device = device
@@ -35,6 +37,24 @@ class Calibrator:
     def close(self):
         """release the resident engine (also happens when the Calibrator is collected)"""
         self._resident.close()
+
+    def setFixed(self, fixed):
+        """Shared parameters every refinement of this Calibrator holds fixed (none by default; the reference has no
+        such switch): names of distortionModel.sharedParameterNames() or the aliases "skew", "focal",
+        "principal_point", "tangential", "intrinsics", "distortion", "all" -- an iterable of them, a mapping
+        name -> value, or an integer mask. A parameter named without a value keeps the start point's value; one with
+        a value has it written into the start point first (fixed={"skew": 0.0}: the closed-form start has gamma != 0)."""
+        self._fixedMask, self._fixedValues = fixedmod.resolveFixed(self._distortionModel.sharedParameterNames(), fixed)
+
+    @property
+    def fixedMask(self):
+        return self._fixedMask
+
+    def _startPoint(self, P0):
+        """the start point of a refinement: P0 with the values of setFixed written in"""
+        if not self._fixedValues:
+            return P0
+        return fixedmod.applyFixedValues(P0, self._fixedValues)
 
     # ---- full pipeline (host initialisation + device refinement) -------------------------
     def calibrate(self, allDetections, maxIters):
@@ -113,6 +133,8 @@ class Calibrator:
 
     def _refineOn(self, eng, P0, maxIters, shouldPrint):
         t0 = time.perf_counter()
+        eng.setFixedShared(self._fixedMask)
+        P0 = self._startPoint(P0)
         if not shouldPrint:
             out = eng.refine(P0, maxIters, self._λinitial, self._λmin, self._λmax, self._Pt_error_min)
         else:
@@ -136,6 +158,29 @@ class Calibrator:
             if eng.lmDone():
                 break
         return eng.lmEnd()
+
+    # ---- pose-only refinement: the camera is known, the views decouple ---------------------
+    def refinePoses(self, A, Winitial, k, allDetections, maxIters):
+        """LM over the poses alone with A and k as given, every view with its own lambda, accept decision and stop
+        (calib_refine_poses; setFixed plays no part). -> (ssePerView (M,), W list of (4,4), iters (M,), status (M,)):
+        status 0, or E_SINGULAR for a view that kept its input pose."""
+        modelId = self._distortionModel.modelId
+        L = engine.NUM_SHARED[modelId]
+        P = engine.composeParameters(modelId, A, Winitial, k, self._device)
+        offs, sensor, model = engine.packDetections(allDetections)
+        sse, poses, iters, status = engine.refinePoses(modelId, P[:L], P[L:].reshape(-1, 6), offs, sensor, model,
+                                                       operator.index(maxIters), self._λinitial, self._λmin, self._λmax,
+                                                       self._Pt_error_min, self._device)
+        _, W, _ = engine.decomposeParameters(modelId, np.concatenate((P[:L], poses.ravel())), self._device)
+        return sse, list(W), iters, status
+
+    def estimatePoses(self, A, k, allDetections, maxIters=20):
+        """Board poses from detections with a known camera: homographies (DLT + LM polish) -> closed-form extrinsics
+        (src/linearcalibrate.py:306-371) -> refinePoses. -> (ssePerView, W, iters, status)"""
+        offs, sensor, model = engine.packDetections(allDetections)
+        Hs = engine.estimateHomographies(offs, sensor, model, 20, self._device)
+        Winitial = engine.computeExtrinsics(Hs, A, self._device)
+        return self.refinePoses(A, Winitial, k, allDetections, maxIters)
 
     def _initializeJacobian(self):
         # src/calibrate.py:173-176; instantaneous here (no symbolic differentiation)

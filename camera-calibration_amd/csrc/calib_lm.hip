@@ -130,6 +130,7 @@ struct calib_handle_s {
     DevBuf<uint32_t> emit_tab;    // fused kernel's record assembly table (buildEmitTable)
     DevBuf<int32_t> stream_ops;   // fused_stream_kernel's per-lane record offsets (buildStreamOps)
     int lm_mode = CALIB_LM_FUSED;
+    uint32_t fixed_mask = 0;      // shared parameters the LM holds fixed (calib_set_fixed_shared); read by calib_lm_begin
     int num_cus = 256;
     DevBuf<int64_t> item_pt0;
     DevBuf<double> sse_part, G[2], bpart, part, red_own, P[2], Peval, trace;
@@ -516,7 +517,7 @@ int64_t numParams(const calib_handle_s* h) { return h->L + 6 * h->M; }
 // ============================================================================ C-ABI
 extern "C" {
 
-int calib_version(void) { return 400; }   // 4.0: 768-byte records, calib_set_problem_views, one-lane-per-view update kernel
+int calib_version(void) { return 410; }   // 4.1: calib_set_fixed_shared / calib_get_fixed_shared, calib_refine_poses
 
 const char* calib_last_error(void) { return g_err.c_str(); }
 
@@ -678,6 +679,20 @@ int calib_fused_form(calib_handle_t h, int* out_share, int* out_waves) {
 int calib_num_shared(calib_handle_t h, int* out_L) {
     if (!h || !out_L) return fail(CALIB_E_INVALID, "null argument");
     *out_L = h->L;
+    return CALIB_OK;
+}
+
+int calib_set_fixed_shared(calib_handle_t h, uint32_t mask) {
+    CHECK_H(h);
+    if (mask >> h->L) return fail(CALIB_E_INVALID, "fixed mask has a bit at or above the number of shared parameters");
+    h->fixed_mask = mask;
+    return CALIB_OK;
+}
+
+int calib_get_fixed_shared(calib_handle_t h, uint32_t* out_mask) {
+    CHECK_H(h);
+    if (!out_mask) return fail(CALIB_E_INVALID, "out_mask is null");
+    *out_mask = h->fixed_mask;
     return CALIB_OK;
 }
 
@@ -1011,6 +1026,7 @@ int calib_lm_begin(calib_handle_t h, const double* P0, int max_iters, double lam
         s.notify = h->host_done_dev;
     }
     s.cur = 1;            // round 0 evaluates the "candidate" buffer 0 == P0
+    s.fixed_mask = (int)h->fixed_mask;     // the update kernel carries it from round to round
     s.max_iters = max_iters;
     HIP_TRY(hipMemsetAsync(h->st.p, 0, 2 * sizeof(LMState), h->stream));
     HIP_TRY(hipMemcpyAsync(h->st.p, &s, sizeof(s), hipMemcpyHostToDevice, h->stream));
@@ -1595,6 +1611,56 @@ int calib_estimate_homographies(int64_t num_views, const int64_t* view_offsets, 
             if (view_offsets[i + 1] - view_offsets[i] < 4)
                 return fail(CALIB_E_INVALID, "a homography needs at least 4 point correspondences per view");
     return homography_pipeline(num_views, view_offsets, sensor_uv, model_xyz, H_out, true, refine_iters, device_id);
+}
+
+int calib_refine_poses(int model, int64_t num_views, const int64_t* view_offsets, const double* sensor_uv,
+                       const double* model_xyz, const double* shared, double* poses_inout, int max_iters,
+                       double lam_init, double lam_min, double lam_max, double err_min, double* out_sse,
+                       int* out_iters, int* out_status, int device_id) {
+    if (model != CALIB_MODEL_RADTAN && model != CALIB_MODEL_FISHEYE)
+        return fail(CALIB_E_INVALID, "unknown distortion model");
+    if (max_iters <= 0) return fail(CALIB_E_INVALID, "max_iters must be >= 1");
+    if (!shared || (num_views > 0 && !poses_inout)) return fail(CALIB_E_INVALID, "null argument");
+    int rc = check_views(num_views, view_offsets, sensor_uv, model_xyz);
+    if (rc || num_views == 0) return rc;
+    rc = use_device(device_id);
+    if (rc) return rc;
+    const int L = model == CALIB_MODEL_RADTAN ? 10 : 9;
+    const int64_t MN = view_offsets[num_views];
+    const size_t M = (size_t)num_views;
+    DevBuf<int64_t> doffs;
+    DevBuf<double> duv, dxyz, dshared, dposes, dsse;
+    DevBuf<int> dint;             // iterations [0, M), status [M, 2 M)
+    hipError_t e = doffs.alloc(M + 1);
+    if (e == hipSuccess) e = duv.alloc((size_t)std::max<int64_t>(MN, 1) * 2);
+    if (e == hipSuccess) e = dxyz.alloc((size_t)std::max<int64_t>(MN, 1) * 3);
+    if (e == hipSuccess) e = dshared.alloc((size_t)L);
+    if (e == hipSuccess) e = dposes.alloc(M * 6);
+    if (e == hipSuccess) e = dsse.alloc(M);
+    if (e == hipSuccess) e = dint.alloc(2 * M);
+    if (e == hipSuccess) e = hipMemcpy(doffs.p, view_offsets, (M + 1) * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess && MN) e = hipMemcpy(duv.p, sensor_uv, (size_t)MN * 16, hipMemcpyHostToDevice);
+    if (e == hipSuccess && MN) e = hipMemcpy(dxyz.p, model_xyz, (size_t)MN * 24, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dshared.p, shared, (size_t)L * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dposes.p, poses_inout, M * 48, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        const dim3 grid((unsigned)((num_views + 15) / 16)), block(256);
+        const double2* uv2 = reinterpret_cast<const double2*>(duv.p);
+        if (model == CALIB_MODEL_RADTAN)
+            hipLaunchKernelGGL((pose_lm_kernel<kRadtan>), grid, block, 0, 0, doffs.p, uv2, dxyz.p, dshared.p, num_views,
+                               max_iters, lam_init, lam_min, lam_max, err_min, dposes.p, dsse.p, dint.p, dint.p + M);
+        else
+            hipLaunchKernelGGL((pose_lm_kernel<kFisheye>), grid, block, 0, 0, doffs.p, uv2, dxyz.p, dshared.p, num_views,
+                               max_iters, lam_init, lam_min, lam_max, err_min, dposes.p, dsse.p, dint.p, dint.p + M);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(poses_inout, dposes.p, M * 48, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out_sse) e = hipMemcpy(out_sse, dsse.p, M * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out_iters) e = hipMemcpy(out_iters, dint.p, M * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out_status) e = hipMemcpy(out_status, dint.p + M, M * 4, hipMemcpyDeviceToHost);
+    doffs.release(); duv.release(); dxyz.release(); dshared.release(); dposes.release(); dsse.release(); dint.release();
+    if (e != hipSuccess) return fail(CALIB_E_HIP, hipGetErrorString(e));
+    return CALIB_OK;
 }
 
 int calib_homography_jacobian(int64_t n, const double* h9, const double* model_xyz, double* out_J, int device_id) {

@@ -125,7 +125,7 @@ struct LMState {
     int done;
     int error;
     int accepted_last;
-    int pad;
+    int fixed_mask; // bit i: shared parameter i is held fixed (calib_set_fixed_shared); carried from round to round
     int* notify;    // host-visible word the writer sets when the loop is over (null: none), so that a host that runs
                     // ahead of the device can stop enqueueing rounds without synchronising
     double dc[kMaxL];
@@ -1880,6 +1880,21 @@ __device__ __forceinline__ bool lm_update_step(const LMState* __restrict__ in, L
     row[L] = gci - (useB ? rhsB : rhsA);
 #pragma unroll
     for (int j = 0; j < L; ++j) if (j == i) row[j] += lam * brow[j];
+    // Fixed shared parameters: the step of the problem whose Jacobian lacks their columns. Deleting columns of J takes
+    // the matching sub-matrix of J^T J, and the Schur complement over the view blocks is entry-wise in the rows of E,
+    // so it is the reduced system that is edited: a fixed lane's row becomes the unit row with right-hand side 0 (dc
+    // exactly 0), every other row loses its fixed columns. The mask is uniform, so mask 0 -- the default -- branches
+    // round the selects: they sit on the one wave's chain in front of the solve (0.12 us of c2's 16.5 us round).
+    const int fixed_mask = in->fixed_mask;
+    const bool fixed_i = (fixed_mask >> i) & 1;
+    if (fixed_mask != 0) {
+#pragma unroll
+        for (int j = 0; j < L; ++j) {
+            const bool fixed_j = (fixed_mask >> j) & 1;
+            row[j] = (fixed_i || fixed_j) ? (j == i ? 1.0 : 0.0) : row[j];
+        }
+        row[L] = fixed_i ? 0.0 : row[L];
+    }
     if (!done) {
         double saved[L + 1];
 #pragma unroll
@@ -1905,13 +1920,13 @@ __device__ __forceinline__ bool lm_update_step(const LMState* __restrict__ in, L
 #pragma unroll
             for (int c = 0; c < L; ++c) if (c == i) dci = dc[c];
             out->dc[i] = dci;
-            if (!done) Pb[cur ^ 1][i] = Pb[cur][i] + dci;
+            if (!done) Pb[cur ^ 1][i] = fixed_i ? Pb[cur][i] : Pb[cur][i] + dci;      // a fixed parameter keeps its bits
         }
         if (w0) {
             out->lam = lam; out->err_cur = err_cur_new; out->last_err = last_err;
             out->lam_min = in->lam_min; out->lam_max = in->lam_max; out->err_min = in->err_min;
             out->cur = cur; out->round = round + 1; out->iters = iters; out->max_iters = in->max_iters;
-            out->done = done ? 1 : 0; out->error = error; out->accepted_last = accepted; out->pad = 0;
+            out->done = done ? 1 : 0; out->error = error; out->accepted_last = accepted; out->fixed_mask = fixed_mask;
             out->notify = in->notify;
             if (done && in->notify) __hip_atomic_store(in->notify, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
@@ -2238,6 +2253,129 @@ __global__ __launch_bounds__(256) void homography_lm_kernel(const int64_t* __res
     }
 #pragma unroll
     for (int j = 0; j < 9; ++j) if (i == j) H[view * 9 + j] = h[j] / h[8];       // Href /= Href[2,2]
+}
+
+// ---------------------------------------------------------------- per-view pose LM (known camera)
+// The refinement with EVERY shared parameter fixed: the views decouple, so each one runs the loop of
+// src/calibrate.py:143-171 on its own six parameters (rho in degrees, t) with its own lambda, accept decision and
+// stop -- 16 lanes per view, 16 views per workgroup, the whole loop inside one launch (the pattern of
+// homography_lm_kernel). Per iteration: the view constants of the pose (the arithmetic of view_setup_kernel), the
+// lanes stride over the view's points with jacobian_point (only the six view columns and the residual are used; the
+// shared columns are dead code), 21 + 6 + 1 sums reduced over the group, V + lam diag V factored redundantly per lane
+// (cholesky6), the candidate's error from project_point. Outputs per view: the pose, the error BEFORE the last
+// update (the reference's return convention; NaN when no iteration ran), iterations executed, and status 0 or -3
+// (CALIB_E_SINGULAR: fewer than three points, or a pivot that is not positive; such a view keeps its input pose).
+__device__ __forceinline__ void pose_view_constants(const double (&e)[6], double (&o)[kViewStride]) {
+    const double deg = 0.017453292519943295;
+    double s[3], c[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double th = e[a] * deg;
+        sincos(th, &s[a], &c[a]);
+        if (fabs(th) <= 1e-8) { s[a] = 0.0; c[a] = 1.0; }
+    }
+    const double sx = s[0], cx = c[0], sy = s[1], cy = c[1], sz = s[2], cz = c[2];
+    o[0] = cz * cy;  o[1] = cz * sy * sx - sz * cx;  o[2] = cz * sy * cx + sz * sx;
+    o[3] = sz * cy;  o[4] = sz * sy * sx + cz * cx;  o[5] = sz * sy * cx - cz * sx;
+    o[6] = -sy;      o[7] = cy * sx;                 o[8] = cy * cx;
+    o[9] = e[3];  o[10] = e[4];  o[11] = e[5];
+    o[12] = deg * cz * cy;  o[13] = deg * sz * cy;  o[14] = -deg * sy;
+    o[15] = -deg * sz;      o[16] = deg * cz;       o[17] = 0.0;
+}
+
+template <int MODEL>
+__global__ __launch_bounds__(256) void pose_lm_kernel(const int64_t* __restrict__ offs, const double2* __restrict__ uv,
+                                                      const double* __restrict__ xyz, const double* __restrict__ shared,
+                                                      int64_t M, int max_iters, double lam_init, double lam_min,
+                                                      double lam_max, double err_min, double* __restrict__ poses,
+                                                      double* __restrict__ out_sse, int* __restrict__ out_iters,
+                                                      int* __restrict__ out_status) {
+    constexpr int L = ModelTraits<MODEL>::L, C = ModelTraits<MODEL>::C;
+    const int tid = threadIdx.x, i = tid & 15;
+    const int64_t view = (int64_t)blockIdx.x * 16 + (tid >> 4);
+    if (view >= M) return;                     // whole 16-lane group together
+    const int64_t p0 = offs[view];
+    const int n = (int)(offs[view + 1] - p0);
+    Shared<MODEL, double> sp;
+    sp.load(shared);
+    double e[6], e_in[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) { e_in[j] = poses[view * 6 + j]; e[j] = e_in[j]; }
+    double lam = lam_init, last_err = __builtin_nan("");
+    int iters = 0, status = n >= 3 ? 0 : -3;
+    bool active = n >= 3;
+    for (int it = 0; it < max_iters && active; ++it) {
+        double vc[kViewStride];
+        pose_view_constants(e, vc);
+        double V[21], g[6], err0 = 0.0;
+#pragma unroll
+        for (int j = 0; j < 21; ++j) V[j] = 0.0;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) g[j] = 0.0;
+        for (int q = i; q < n; q += 16) {
+            const double2 m = uv[p0 + q];
+            const double* X = xyz + 3 * (p0 + q);
+            double u, v;
+            double2 J[C];
+            jacobian_point<MODEL, double>(sp, vc, X[0], X[1], X[2], u, v, J);
+            const double ru = m.x - u, rv = m.y - v;
+#pragma unroll
+            for (int a = 0; a < 6; ++a) {
+#pragma unroll
+                for (int b = 0; b <= a; ++b) V[tri(a, b)] += J[L + a].x * J[L + b].x + J[L + a].y * J[L + b].y;
+                g[a] += J[L + a].x * ru + J[L + a].y * rv;
+            }
+            err0 += ru * ru + rv * rv;
+        }
+#pragma unroll
+        for (int j = 0; j < 21; ++j) V[j] = group_sum16(V[j]);
+#pragma unroll
+        for (int j = 0; j < 6; ++j) g[j] = group_sum16(g[j]);
+        err0 = group_sum16(err0);
+        double invd[6], z[6], d[6];
+        const bool ok = eliminate(V, g, lam, invd, z);       // V becomes the Cholesky factor of V + lam diag V
+        backward6(V, invd, z, d);
+        iters = it + 1;
+        last_err = err0;
+        if (!ok) {                                           // per-view failure: the input pose goes back
+#pragma unroll
+            for (int j = 0; j < 6; ++j) e[j] = e_in[j];
+            status = -3;
+            break;
+        }
+        double e1[6], err1 = 0.0;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) e1[j] = e[j] + d[j];
+        pose_view_constants(e1, vc);
+        for (int q = i; q < n; q += 16) {
+            const double2 m = uv[p0 + q];
+            const double* X = xyz + 3 * (p0 + q);
+            double u, v;
+            project_point<MODEL, double>(sp, vc, X[0], X[1], X[2], u, v);
+            const double ru = m.x - u, rv = m.y - v;
+            err1 += ru * ru + rv * rv;
+        }
+        err1 = group_sum16(err1);
+        if (err1 < err0) {                                   // strict, NaN rejects (src/calibrate.py:161)
+#pragma unroll
+            for (int j = 0; j < 6; ++j) e[j] = e1[j];
+            lam = lam / 10;
+        } else {
+            lam = lam * 10;
+        }
+        active = (lam_min < lam && lam < lam_max) && !(err0 < err_min);
+    }
+    if (i < 6) {
+        double ev = e[0];
+#pragma unroll
+        for (int j = 1; j < 6; ++j) ev = (i == j) ? e[j] : ev;
+        poses[view * 6 + i] = ev;
+    }
+    if (i == 0) {
+        if (out_sse) out_sse[view] = last_err;
+        if (out_iters) out_iters[view] = iters;
+        if (out_status) out_status[view] = status;
+    }
 }
 
 // HomographyJacobian.compute (src/jacobian.py:88-121): rows (du, dv)/dh of the projection of (X, Y, 1)

@@ -9,6 +9,7 @@ import numpy as np
 
 from . import _native as nat
 from . import engine
+from . import fixed
 
 
 class DistortionModel:
@@ -23,6 +24,11 @@ class DistortionModel:
 
     def getDistortionSymbols(self):
         raise NotImplementedError()
+
+    def sharedParameterNames(self):
+        """names of the L shared parameters in the order of the parameter vector P: what Calibrator(fixed=...)
+        and RefineEngine.setFixedShared take (fixed.py lists the aliases)"""
+        return fixed.INTRINSIC_NAMES + tuple(self.getDistortionSymbols())
 
     def projectWithDistortion(self, A, X, k):
         """A (3,3), X (N,3) camera-frame points, k -> (N,2) sensor points (src/distortion.py:42-59)"""

@@ -255,19 +255,41 @@ def _raiseTogether(dist, torch, err, device):
         raise RuntimeError("refineDistributed: another rank rejected its shard; see that rank's error")
 
 
+def _agreeOnFixedMask(dist, torch, mask, err, device):
+    """Every rank solves the same L x L system, so every rank must fix the same shared parameters: one MAX
+    all-reduce of (mask, -mask) gives the largest and the smallest mask of the group (a rank whose `fixedShared` did
+    not resolve contributes -1). A rank with an error of its own re-raises it; every other rank raises too."""
+    t = torch.tensor([mask, -mask], dtype=torch.int64, device=device)
+    dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    hi, lo = int(t[0].item()), -int(t[1].item())
+    if err is not None:
+        raise err
+    if lo < 0:
+        raise RuntimeError("refineDistributed: another rank rejected its fixedShared; see that rank's error")
+    if lo != hi:
+        raise ValueError(f"refineDistributed: the ranks disagree on fixedShared (masks between {lo:#x} and {hi:#x}, "
+                         f"this rank {mask:#x}); every rank must fix the same shared parameters")
+
+
 def refineDistributed(modelName, P0, viewOffsets, sensorPoints, modelPoints, maxIters, dtype="f64",
-                      checkEvery=8, engineFactory=None, allReduceFactory=None, **lmOptions):
+                      checkEvery=8, engineFactory=None, allReduceFactory=None, fixedShared=(), **lmOptions):
     """Refine ONE global problem with the views sharded over the ranks of the default
     torch.distributed process group (every rank passes the same global arrays and gets the same
     global result back). -> (sse, P (K,), iters, trace)
 
     engineFactory(viewOffsets, sensor, model) / allReduceFactory(engine) exist so that the protocol
     can be exercised without GPUs (tests); by default the shard engine is a RefineEngine on
-    cuda:LOCAL_RANK and the reduction a torch.distributed.all_reduce (RCCL) on its stream."""
+    cuda:LOCAL_RANK and the reduction a torch.distributed.all_reduce (RCCL) on its stream.
+
+    fixedShared: shared parameters held fixed, as Calibrator.setFixed takes them (names, aliases, a mapping
+    name -> value, or a mask). Every rank must pass the same; the ranks check that they agree and raise together if
+    not. An engine made by engineFactory receives the mask through its setFixedShared method; one without that
+    method cannot take a non-empty mask (TypeError)."""
     import os
     import torch
     import torch.distributed as dist
     from . import engine as engine_mod
+    from . import fixed as fixed_mod
     rank, world = dist.get_rank(), dist.get_world_size()
     L = engine_mod.NUM_SHARED[engine_mod.MODEL_IDS[modelName]]
     validateGlobalProblem(viewOffsets)                 # identical on every rank: everybody raises, or nobody
@@ -292,6 +314,15 @@ def refineDistributed(modelName, P0, viewOffsets, sensorPoints, modelPoints, max
     except Exception as e:           # noqa: BLE001 -- re-raised below, after every rank knows
         err = e
     _raiseTogether(dist, torch, err, okDevice)
+    fixedMask, fixedValues = -1, {}
+    try:
+        fixedMask, fixedValues = fixed_mod.resolveFixed(fixed_mod.sharedNames(engine_mod.MODEL_IDS[modelName]),
+                                                        fixedShared)
+    except Exception as e:           # noqa: BLE001 -- re-raised by _agreeOnFixedMask, after every rank knows
+        err = e
+    _agreeOnFixedMask(dist, torch, fixedMask, err, okDevice)
+    if fixedValues:
+        Pl = fixed_mod.applyFixedValues(Pl, fixedValues)
     if onGpu:
         # CALIB_ALLREDUCE = auto (default) | direct | torch | peer. auto = RCCL: the library's own ncclAllReduce
         # (whole rounds from C), else torch.distributed.all_reduce. peer = the exchange inside the reduce kernel,
@@ -314,6 +345,10 @@ def refineDistributed(modelName, P0, viewOffsets, sensorPoints, modelPoints, max
     # before anybody enters the collective
     try:
         lm.maxIters = int(maxIters)
+        if hasattr(eng, "setFixedShared"):
+            eng.setFixedShared(fixedMask)
+        elif fixedMask:
+            raise TypeError(f"{type(eng).__name__} has no setFixedShared method: it cannot hold shared parameters fixed")
         eng.lmBegin(Pl, maxIters, **lmOptions)
     except Exception as e:           # noqa: BLE001
         err = e

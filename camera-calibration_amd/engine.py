@@ -8,6 +8,7 @@ import ctypes
 import numpy as np
 
 from . import _native as nat
+from . import fixed as fixedmod
 
 LAMBDA_INITIAL = 1e-3      # Calibrator._λinitial      src/calibrate.py:13
 LAMBDA_MIN = 1e-10         # Calibrator._λmin          src/calibrate.py:14
@@ -194,6 +195,21 @@ class RefineEngine:
         """'fused' (default) or 'two_kernel' (materialise the compact J in HBM), see calib_lm.h."""
         ids = {"fused": nat.LM_FUSED, "two_kernel": nat.LM_TWO_KERNEL}
         nat.check(self._lib.calib_set_lm_mode(self._h, ids[mode] if isinstance(mode, str) else int(mode)))
+
+    def setFixedShared(self, fixed):
+        """Hold shared parameters fixed in every LM loop begun from now on (calib_set_fixed_shared): an integer
+        mask (bit i = shared parameter i in the order of P), a name, an iterable of names or a mapping whose keys
+        are names (fixed.py: names and aliases). Only WHICH parameters are fixed is taken from it -- they keep the
+        start point's values; Calibrator(fixed={name: value}) writes values into the start point."""
+        mask, _ = fixedmod.resolveFixed(fixedmod.sharedNames(self.modelId), fixed)
+        nat.check(self._lib.calib_set_fixed_shared(self._h, mask))
+
+    @property
+    def fixedShared(self):
+        """the mask of fixed shared parameters the handle holds (calib_get_fixed_shared)"""
+        m = ctypes.c_uint32(0)
+        nat.check(self._lib.calib_get_fixed_shared(self._h, ctypes.byref(m)))
+        return m.value
 
     def fusedForm(self):
         """-> (share, waves): share > 0 when the loaded problem's fused rounds run in the stream form (4-point groups
@@ -493,6 +509,31 @@ def refineHomographies(Hs, viewOffsets, sensorPoints, modelPoints, maxIters=20, 
     nat.check(nat.loadLibrary().calib_refine_homographies(H.shape[0], nat.i64ptr(offs), nat.dptr(s), nat.dptr(m),
                                                           nat.dptr(H), int(maxIters), int(device)))
     return H
+
+
+def refinePoses(modelId, shared, poses, viewOffsets, sensorPoints, modelPoints, maxIters=20, lamInit=LAMBDA_INITIAL,
+                lamMin=LAMBDA_MIN, lamMax=LAMBDA_MAX, errMin=PT_ERROR_MIN, device=0):
+    """Pose-only LM with a known camera, every view on its own (calib_refine_poses): shared (L,) in the order of P,
+    poses (M,6) rows (rho_x, rho_y, rho_z [degrees], t). -> (ssePerView (M,) [pre-update, as the reference returns],
+    poses (M,6), iters (M,), status (M,)): status 0, or E_SINGULAR for a view that kept its input pose."""
+    shared = np.ascontiguousarray(np.asarray(shared, dtype=np.float64).ravel())
+    if shared.shape[0] != NUM_SHARED[modelId]:
+        raise ValueError(f"Expected {NUM_SHARED[modelId]} shared parameters, got {shared.shape[0]}")
+    offs, s, m = _packedViews(viewOffsets, sensorPoints, modelPoints)
+    M = offs.shape[0] - 1
+    e = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 6)).copy()
+    if e.shape[0] != M:
+        raise ValueError(f"Expected {M} poses, got {e.shape[0]}")
+    sse = np.empty(M)
+    iters = np.zeros(M, dtype=np.int32)
+    status = np.zeros(M, dtype=np.int32)
+    nat.requireDevice()
+    nat.check(nat.loadLibrary().calib_refine_poses(
+        modelId, M, nat.i64ptr(offs), nat.dptr(s), nat.dptr(m), nat.dptr(shared), nat.dptr(e), int(maxIters),
+        float(lamInit), float(lamMin), float(lamMax), float(errMin), nat.dptr(sse),
+        iters.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+        int(device)))
+    return sse, e, iters, status
 
 
 def composeParameters(modelId, A, W, k, device=0):

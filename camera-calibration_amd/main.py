@@ -14,7 +14,8 @@ _MODELS = {
 
 def calibrateCamera(allDetections: list, distortionType: str, maxIters, **engineOptions) -> tuple:
     """allDetections: per view a (sensorPoints (N,2), modelPoints (N,3)) pair; distortionType one of
-    "radtan", "fisheye"; engineOptions: dtype="f64"|"f32", device=<HIP device> (extras).
+    "radtan", "fisheye"; engineOptions: dtype="f64"|"f32", device=<HIP device>, fixed=<shared parameters the
+    refinement holds fixed, e.g. {"skew": 0.0} or ("k3",): Calibrator.setFixed> (extras).
 
     Host closed-form initialisation, then the Levenberg-Marquardt refinement on the GPU.
     Returns the final sum of squared errors, the intrinsic matrix (3,3), the list of world-to-camera
@@ -24,3 +25,13 @@ def calibrateCamera(allDetections: list, distortionType: str, maxIters, **engine
     except KeyError:
         raise ValueError(f"Distortion type: {distortionType} unknown") from None
     return calibrate.Calibrator(modelClass(), **engineOptions).calibrate(allDetections, maxIters)
+
+
+def estimatePoses(allDetections: list, distortionType: str, A, k, maxIters=20, **engineOptions) -> tuple:
+    """Board poses of detections taken with a KNOWN camera (A (3,3), k): closed-form start, then the per-view
+    pose-only refinement on the GPU. Returns (ssePerView (M,), W list of (4,4), iters (M,), status (M,))."""
+    try:
+        modelClass = _MODELS[distortionType]
+    except KeyError:
+        raise ValueError(f"Distortion type: {distortionType} unknown") from None
+    return calibrate.Calibrator(modelClass(), **engineOptions).estimatePoses(A, k, allDetections, maxIters)

@@ -107,6 +107,18 @@ int calib_fused_form(calib_handle_t h, int* out_share, int* out_waves);
 int calib_num_shared(calib_handle_t h, int* out_L);          /* L                          */
 int calib_num_params(calib_handle_t h, int64_t* out_K);       /* K = L + 6*num_views        */
 
+/* Hold chosen SHARED parameters fixed in the LM loop (the reference refines all of them; this is surface beside the
+ * drop-in one). Bit i of mask = shared parameter i in the order of P (bit 0 alpha, 1 beta, 2 gamma, 3 uc, 4 vc, 5.. the
+ * distortion coefficients); a bit >= L is CALIB_E_INVALID. Every LM step is then the step of the problem whose
+ * Jacobian has those columns deleted -- delta_free = (Jf^T Jf + lambda diag(Jf^T Jf))^-1 Jf^T r, delta_fixed = 0 -- and a
+ * fixed parameter keeps the bits of the start point; error, accept rule, lambda schedule and stop rule are unchanged.
+ * The mask takes effect at the next calib_lm_begin (hence calib_refine, calib_refine_awk, calib_lm_step_delta and the
+ * sharded loop, where every rank must set the same mask) and stays on the handle across problems. All L bits set is
+ * legal: only the poses move (calib_refine_poses does that per view, without the global loop). Mask 0, the default,
+ * is bit for bit the loop without this call. calib_eval and calib_normal_eq are not affected. */
+int calib_set_fixed_shared(calib_handle_t h, uint32_t mask);
+int calib_get_fixed_shared(calib_handle_t h, uint32_t* out_mask);
+
 /* One evaluation at P. Any output may be NULL.
  *   out_y   (MN,2)    projection            -> Calibrator.projectAllPoints
  *   out_r   (MN,2)    sensor - projection   -> residual of src/calibrate.py:151
@@ -245,6 +257,18 @@ int calib_project_with_distortion(int model, int64_t n, const double* A, const d
  * only X, Y are used. max_iters = 20 in the reference. */
 int calib_refine_homographies(int64_t num_views, const int64_t* view_offsets, const double* sensor_uv,
                               const double* model_xyz, double* H_inout, int max_iters, int device_id);
+
+/* Pose-only refinement with a KNOWN camera: every view runs the loop of src/calibrate.py:143-171 on its own six
+ * parameters, with its own lambda, accept decision and stop, all views in one launch. shared (L): the camera in the
+ * order of P; poses_inout (M,6): per view rho_x, rho_y, rho_z [DEGREES], t -- start values in, refined out.
+ * Per view (each may be NULL): out_sse = the view's error before its last update (the reference's return
+ * convention; NaN when no iteration ran), out_iters = iterations executed, out_status = 0 or CALIB_E_SINGULAR (fewer
+ * than three points, or V + lambda diag V has a pivot that is not positive); such a view keeps its input pose and
+ * does not fail the call. max_iters <= 0 is CALIB_E_INVALID. Needs no handle. */
+int calib_refine_poses(int model, int64_t num_views, const int64_t* view_offsets, const double* sensor_uv,
+                       const double* model_xyz, const double* shared, double* poses_inout, int max_iters,
+                       double lam_init, double lam_min, double lam_max, double err_min, double* out_sse,
+                       int* out_iters, int* out_status, int device_id);
 
 /* HomographyJacobian.compute (src/jacobian.py:88-121): the (2N, 9) Jacobian of the projection of the
  * model points (X, Y, 1) through H = h.reshape(3,3) with respect to h, rows (u_j, v_j) interleaved.
