@@ -89,6 +89,12 @@ SIGNATURES = {
     "calib_rccl_selftest": (ctypes.c_int, [_h, ctypes.c_double]),
     "calib_rccl_shutdown": (ctypes.c_int, [_h]),
     "calib_lm_allreduce": (ctypes.c_int, [_h]),
+    "calib_view_errors": (ctypes.c_int, [_h, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
+    "calib_cov_local": (ctypes.c_int, [_h, _c_double_p]),
+    "calib_cov_finish": (ctypes.c_int, [_h, ctypes.c_int64, ctypes.c_int64, _c_double_p, _c_int64_p, _c_double_p,
+                                        _c_double_p, _c_double_p, _c_double_p]),
+    "calib_covariance": (ctypes.c_int, [_h, _c_double_p, _c_double_p, _c_int64_p, _c_double_p, _c_double_p,
+                                        _c_double_p, _c_double_p]),
     "calib_profile_enable": (ctypes.c_int, [_h, ctypes.c_int]),
     "calib_profile_read": (ctypes.c_int, [_h, ctypes.c_int, _c_double_p, _c_int64_p]),
 }

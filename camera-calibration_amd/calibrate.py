@@ -16,6 +16,7 @@ from . import engine
 from . import fixed as fixedmod
 from . import jacobian
 from . import mathutils as mu
+from . import uncertainty as uncertaintymod
 
 
 class Calibrator:
@@ -62,6 +63,26 @@ class Calibrator:
         Ainitial, Winitial, kInitial = self.estimateCalibrationParameters(allDetections)
         return self.refineCalibrationParameters(Ainitial, Winitial, kInitial, allDetections,
                                                 maxIters, shouldPrint=True)
+
+    def calibrateExtended(self, allDetections, maxIters):
+        """calibrate() plus how far to trust it -> (sse, Afinal, Wfinal, kFinal, uncertainty): the first four exactly
+        as calibrate() returns them, the fifth a CalibrationUncertainty evaluated at the refined parameters on the
+        problem the refinement left resident in HBM."""
+        sse, A, W, k = self.calibrate(allDetections, maxIters)
+        return sse, A, W, k, self.uncertainty(A, W, k, allDetections)
+
+    def uncertainty(self, A, W, k, allDetections):
+        """Standard deviations, covariance and per-view reprojection errors of the estimate (A, W, k) ->
+        uncertainty.CalibrationUncertainty. The covariance is sigma^2 (Jf^T Jf)^-1 with the columns of the
+        parameters in fixedMask deleted (their rows and columns are zero); pose entries are Euler angles in DEGREES,
+        then t. Detections that are the ones just refined are not uploaded again (engine.ResidentProblem)."""
+        P = self._composeParameterVector(A, W, k).ravel()
+        eng = self._resident.getFromDetections(allDetections)
+        eng.setFixedShared(self._fixedMask)
+        cov = eng.covariance(P, wantViews=True, wantCross=False)
+        errs = eng.viewErrors(P)
+        return uncertaintymod.fromEngineResults(self._distortionModel.sharedParameterNames(), cov, errs, eng.MN,
+                                                values=P, fixedMask=self._fixedMask)
 
     def estimateCalibrationParameters(self, allDetections):
         """src/calibrate.py:41-58: Zhang's closed-form initialisation, on the host."""

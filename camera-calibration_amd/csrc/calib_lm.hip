@@ -157,6 +157,14 @@ struct calib_handle_s {
     int lm_max_iters = 0;
     int rounds_enqueued = 0;
 
+    // uncertainty (calib_view_errors, calib_cov_*)
+    bool cov_pending = false;             // calib_cov_local has run its lambda = 0 round; calib_cov_finish is due
+    std::vector<int64_t> ext_offsets;     // the caller's view_offsets (M + 1), uploaded by the first calib_view_errors
+    bool ext_offsets_on_device = false;
+    DevBuf<int64_t> ext_offsets_dev;
+    DevBuf<double> view_err, cov_css, cov_views, cov_cross;
+    DevBuf<int> cov_flag;
+
     // pinned staging of calib_set_problem's uploads (upload_staged)
     bool stage_ready = false;
     void* stage_pinned = nullptr;
@@ -517,7 +525,7 @@ int64_t numParams(const calib_handle_s* h) { return h->L + 6 * h->M; }
 // ============================================================================ C-ABI
 extern "C" {
 
-int calib_version(void) { return 410; }   // 4.1: calib_set_fixed_shared / calib_get_fixed_shared, calib_refine_poses
+int calib_version(void) { return 420; }   // 4.2: calib_view_errors, calib_cov_local / calib_cov_finish / calib_covariance
 
 const char* calib_last_error(void) { return g_err.c_str(); }
 
@@ -747,6 +755,9 @@ int set_problem_impl(calib_handle_t h, int64_t num_views, const int64_t* view_of
     SYNC_H(h);
     h->has_problem = false;
     h->lm_active = false;
+    h->cov_pending = false;
+    h->ext_offsets.assign(view_offsets, view_offsets + num_views + 1);
+    h->ext_offsets_on_device = false;
     h->M = num_views;
     h->MN = MN;
 
@@ -978,6 +989,7 @@ int calib_lm_begin(calib_handle_t h, const double* P0, int max_iters, double lam
     int rc = need_problem(h);
     if (rc) return rc;
     if (!P0) return fail(CALIB_E_INVALID, "P0 is null");
+    h->cov_pending = false;
     if (max_iters <= 0)
         return fail(CALIB_E_INVALID, "max_iters must be >= 1 (the reference raises UnboundLocalError "
                                      "for maxIters=0, src/calibrate.py:171)");
@@ -1271,7 +1283,7 @@ int calib_rccl_selftest(calib_handle_t h, double timeout_s) {
 
 int calib_lm_allreduce(calib_handle_t h) {
     CHECK_H(h);
-    if (!h->lm_active) return fail(CALIB_E_STATE, "calib_lm_begin has not been called");
+    if (!h->lm_active && !h->cov_pending) return fail(CALIB_E_STATE, "calib_lm_begin has not been called");
     if (!h->comm) return fail(CALIB_E_STATE, "calib_rccl_init has not been called");
     const int rc = g_rccl.allReduce(h->red, h->red, (size_t)reduceSize(h->L), kNcclDouble, kNcclSum, h->comm, h->stream);
     if (rc) return rccl_fail("ncclAllReduce", rc);
@@ -1860,5 +1872,187 @@ int calib_profile_read(calib_handle_t h, int which, double* out_total_ms, int64_
     *out_launches = count;
     return CALIB_OK;
 }
+
+}  // extern "C"
+// ---- uncertainty: per-view reprojection errors, parameter covariance -------------------------------------
+namespace {
+template <int MODEL, typename T>
+int launch_view_errors_t(calib_handle_s* h) {
+    using T2 = typename Pair<T>::type;
+    const unsigned blocks = (unsigned)((h->M + kViewErrWaves - 1) / kViewErrWaves);
+    hipLaunchKernelGGL((view_errors_kernel<MODEL, T>), dim3(blocks), dim3(64 * kViewErrWaves), 0, h->stream,
+                       (const double*)h->Peval.p, reinterpret_cast<const T2*>(h->uv.p), reinterpret_cast<const T2*>(h->XY.p),
+                       reinterpret_cast<const T*>(h->Z.p), reinterpret_cast<const T*>(h->VC.p), (const int*)h->pt_view.p,
+                       (const int64_t*)h->ext_offsets_dev.p, h->M, h->view_err.p);
+    LAUNCHED(h, "view_errors_kernel");
+    return CALIB_OK;
+}
+
+template <int L>
+int launch_covariance_views(calib_handle_s* h, double sigma2, bool cross) {
+    const int blocks = std::max(1, std::min((h->nv + kSchurThreads - 1) / kSchurThreads, 4 * h->num_cus));
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kSchurThreads), 0, h->stream, (const double*)h->G[0].p, view_items(h),
+                           (const int*)h->view_ext.p, h->nv, stream_map(h), (const double*)h->cov_css.p, sigma2,
+                           h->cov_views.p, cross ? h->cov_cross.p : nullptr, h->cov_flag.p);
+    };
+    if (h->plan.stream()) launch(covariance_views_kernel<L, true>); else launch(covariance_views_kernel<L, false>);
+    LAUNCHED(h, "covariance_views_kernel");
+    return CALIB_OK;
+}
+
+// sigma2 (S_free)^-1 of the reduced system S = Bsum - Ssub, zero-padded to L x L for the fixed parameters: Cholesky of
+// the free sub-matrix (lower triangle), its inverse by substitution, mirrored so that the result is exactly symmetric.
+// Pure host arithmetic on the all-reduced buffer: every rank of a sharded run gets the same bits.
+bool shared_covariance(const double* red, int L, uint32_t fixed_mask, double sigma2, double* Css /* L*L */) {
+    int idx[kMaxL], n = 0;
+    for (int i = 0; i < L; ++i) if (!((fixed_mask >> i) & 1)) idx[n++] = i;
+    double S[kMaxL][kMaxL], X[kMaxL][kMaxL];
+    for (int a = 0; a < n; ++a)
+        for (int b = 0; b <= a; ++b) S[a][b] = red[idx[a] * L + idx[b]] - red[L * L + idx[a] * L + idx[b]];
+    for (int j = 0; j < n; ++j) {                        // S = Lc Lc^T, in place
+        double d = S[j][j];
+        for (int q = 0; q < j; ++q) d -= S[j][q] * S[j][q];
+        if (!(d > 0.0)) return false;
+        S[j][j] = std::sqrt(d);
+        for (int i = j + 1; i < n; ++i) {
+            double t = S[i][j];
+            for (int q = 0; q < j; ++q) t -= S[i][q] * S[j][q];
+            S[i][j] = t / S[j][j];
+        }
+    }
+    for (int c = 0; c < n; ++c) {                        // column c of the inverse
+        double z[kMaxL];
+        for (int i = 0; i < n; ++i) {
+            double t = i == c ? 1.0 : 0.0;
+            for (int q = 0; q < i; ++q) t -= S[i][q] * z[q];
+            z[i] = t / S[i][i];
+        }
+        for (int i = n - 1; i >= 0; --i) {
+            double t = z[i];
+            for (int q = i + 1; q < n; ++q) t -= S[q][i] * X[q][c];
+            X[i][c] = t / S[i][i];
+        }
+    }
+    std::fill(Css, Css + L * L, 0.0);
+    for (int a = 0; a < n; ++a)
+        for (int b = 0; b <= a; ++b) {
+            const double v = sigma2 * X[a][b];
+            Css[idx[a] * L + idx[b]] = v;
+            Css[idx[b] * L + idx[a]] = v;
+        }
+    return true;
+}
+}  // namespace
+extern "C" {
+
+int calib_view_errors(calib_handle_t h, const double* P, double* out_view_sse, double* out_view_rms,
+                      double* out_view_max) {
+    CHECK_H(h);
+    int rc = need_problem(h);
+    if (rc) return rc;
+    if (!P) return fail(CALIB_E_INVALID, "P is null");
+    if (h->lm_active)       // the running loop owns the view constants this evaluation would overwrite
+        return fail(CALIB_E_STATE, "a stepping LM run is active on this handle (calib_lm_end it first)");
+    const int64_t M = h->M;
+    if (M == 0) return CALIB_OK;
+    if (!h->ext_offsets_on_device) {
+        HIP_TRY(h->ext_offsets_dev.alloc((size_t)M + 1));
+        HIP_TRY(hipMemcpy(h->ext_offsets_dev.p, h->ext_offsets.data(), ((size_t)M + 1) * 8, hipMemcpyHostToDevice));
+        h->ext_offsets_on_device = true;
+    }
+    HIP_TRY(h->view_err.alloc((size_t)M * 3));
+    HIP_TRY(hipMemcpyAsync(h->Peval.p, P, (size_t)numParams(h) * 8, hipMemcpyHostToDevice, h->stream));
+    rc = launch_view_setup_any(h, h->Peval.p, nullptr, h->st_eval.p, 0);
+    if (rc) return rc;
+    if (h->dtype == CALIB_DTYPE_F64)
+        rc = h->model == CALIB_MODEL_RADTAN ? launch_view_errors_t<kRadtan, double>(h) : launch_view_errors_t<kFisheye, double>(h);
+    else
+        rc = h->model == CALIB_MODEL_RADTAN ? launch_view_errors_t<kRadtan, float>(h) : launch_view_errors_t<kFisheye, float>(h);
+    if (rc) return rc;
+    std::vector<double> tmp((size_t)M * 3);
+    HIP_TRY(hipMemcpyAsync(tmp.data(), h->view_err.p, tmp.size() * 8, hipMemcpyDeviceToHost, h->stream));
+    SYNC_H(h);
+    for (int64_t i = 0; i < M; ++i) {
+        if (out_view_sse) out_view_sse[i] = tmp[(size_t)3 * i];
+        if (out_view_rms) out_view_rms[i] = tmp[(size_t)3 * i + 1];
+        if (out_view_max) out_view_max[i] = tmp[(size_t)3 * i + 2];
+    }
+    return CALIB_OK;
+}
+
+int calib_cov_local(calib_handle_t h, const double* P) {
+    CHECK_H(h);
+    if (h->lm_active) return fail(CALIB_E_STATE, "a stepping LM run is active on this handle (calib_lm_end it first)");
+    // the bootstrap round at lambda = 0, as calib_normal_eq runs it: variant A of the reduce buffer then holds Bsum,
+    // Ssub = sum E V^-1 E^T, the count of views whose V has a pivot that is not positive, and sse(P)
+    int rc = calib_lm_begin(h, P, 1, 0.0, 0.0, INFINITY, -INFINITY);
+    if (rc) return rc;
+    rc = calib_lm_local(h);
+    h->lm_active = false;
+    if (rc) return rc;
+    h->cov_pending = true;
+    return CALIB_OK;
+}
+
+int calib_cov_finish(calib_handle_t h, int64_t total_points, int64_t total_views, double* out_sigma2, int64_t* out_dof,
+                     double* out_cov_shared, double* out_cov_views, double* out_cov_cross, double* out_std) {
+    CHECK_H(h);
+    if (h->lm_active) return fail(CALIB_E_STATE, "a stepping LM run is active on this handle (calib_lm_end it first)");
+    if (!h->cov_pending) return fail(CALIB_E_STATE, "calib_cov_local has not been called");
+    h->cov_pending = false;
+    const int L = h->L;
+    const int64_t M = h->M;
+    if (total_points < h->MN || total_views < M) return fail(CALIB_E_INVALID, "totals are smaller than this shard");
+    int nfree = 0;
+    for (int i = 0; i < L; ++i) nfree += !((h->fixed_mask >> i) & 1);
+    const int64_t dof = 2 * total_points - (nfree + 6 * total_views);
+    if (dof <= 0) { SYNC_H(h); return fail(CALIB_E_INVALID, "no degrees of freedom left: 2 n <= number of free parameters"); }
+    std::vector<double> red((size_t)variantSize(L));
+    HIP_TRY(hipMemcpyAsync(red.data(), h->red, red.size() * 8, hipMemcpyDeviceToHost, h->stream));
+    SYNC_H(h);
+    if (red[(size_t)2 * L * L + 2 * L] > 0.0)
+        return fail(CALIB_E_SINGULAR, "Singular matrix: a view's 6 x 6 block has a pivot that is not positive");
+    const double sigma2 = red[(size_t)2 * L * L + 2 * L + 1] / (double)dof;
+    double Css[kMaxL * kMaxL];
+    if (!shared_covariance(red.data(), L, h->fixed_mask, sigma2, Css))
+        return fail(CALIB_E_SINGULAR, "Singular matrix: the reduced system of the shared parameters is not positive definite");
+    if (out_sigma2) *out_sigma2 = sigma2;
+    if (out_dof) *out_dof = dof;
+    if (out_cov_shared) std::memcpy(out_cov_shared, Css, (size_t)L * L * 8);
+    if (out_std) for (int i = 0; i < L; ++i) out_std[i] = std::sqrt(Css[i * L + i]);
+    if (M == 0 || !(out_cov_views || out_cov_cross || out_std)) return CALIB_OK;
+    HIP_TRY(h->cov_css.alloc((size_t)kMaxL * kMaxL));
+    HIP_TRY(h->cov_flag.alloc(1));
+    HIP_TRY(h->cov_views.alloc((size_t)M * 36));
+    if (out_cov_cross) HIP_TRY(h->cov_cross.alloc((size_t)M * L * 6));
+    HIP_TRY(hipMemcpyAsync(h->cov_css.p, Css, (size_t)L * L * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(h->cov_flag.p, 0, sizeof(int), h->stream));
+    const int rc = L == 10 ? launch_covariance_views<10>(h, sigma2, out_cov_cross != nullptr)
+                           : launch_covariance_views<9>(h, sigma2, out_cov_cross != nullptr);
+    if (rc) return rc;
+    int flag = 0;
+    HIP_TRY(hipMemcpyAsync(&flag, h->cov_flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    SYNC_H(h);
+    if (flag)
+        return fail(CALIB_E_SINGULAR, "Singular matrix: a view's 6 x 6 block has a pivot that is not positive");
+    std::vector<double> tmp;
+    double* cv = out_cov_views;
+    if (!cv) { tmp.resize((size_t)M * 36); cv = tmp.data(); }
+    HIP_TRY(hipMemcpy(cv, h->cov_views.p, (size_t)M * 36 * 8, hipMemcpyDeviceToHost));
+    if (out_cov_cross) HIP_TRY(hipMemcpy(out_cov_cross, h->cov_cross.p, (size_t)M * L * 6 * 8, hipMemcpyDeviceToHost));
+    if (out_std)
+        for (int64_t v = 0; v < M; ++v)
+            for (int a = 0; a < 6; ++a) out_std[L + 6 * v + a] = std::sqrt(cv[(size_t)v * 36 + a * 7]);
+    return CALIB_OK;
+}
+
+int calib_covariance(calib_handle_t h, const double* P, double* out_sigma2, int64_t* out_dof, double* out_cov_shared,
+                     double* out_cov_views, double* out_cov_cross, double* out_std) {
+    const int rc = calib_cov_local(h, P);
+    if (rc) return rc;
+    return calib_cov_finish(h, h->MN, h->M, out_sigma2, out_dof, out_cov_shared, out_cov_views, out_cov_cross, out_std);
+}
+
 
 }  // extern "C"

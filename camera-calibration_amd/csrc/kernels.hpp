@@ -2706,4 +2706,161 @@ __global__ void project_cam_kernel(const double* __restrict__ A, const double* _
     out[2 * i + 1] = v;
 }
 
+// ---------------------------------------------------------------- per-view reprojection errors
+// calib_view_errors: one wave per (external) view projects the view's points at P and reduces |r|^2 -- sum and
+// maximum -- in a fixed order: lane l takes points l, l + 64, ... in order, then a shuffle tree. Three doubles per
+// view come out (sum |r|^2, sqrt(sum / n), max |r|); nothing is written per point. The residual is formed in the
+// storage type T exactly as the jacobian kernel forms it and squared in fp64. An empty view writes (0, NaN, 0).
+// Reads 5 T per point and nothing else of size: HBM-bound (40 B / point fp64, 20 B fp32).
+constexpr int kViewErrWaves = 4;
+template <int MODEL, typename T>
+__global__ __launch_bounds__(64 * kViewErrWaves) void view_errors_kernel(
+        const double* __restrict__ P, const typename Pair<T>::type* __restrict__ uv,
+        const typename Pair<T>::type* __restrict__ XY, const T* __restrict__ Z, const T* __restrict__ VC,
+        const int* __restrict__ pt_view, const int64_t* __restrict__ view_offsets, int64_t M,
+        double* __restrict__ out /* (M, 3) */) {
+    using T2 = typename Pair<T>::type;
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * kViewErrWaves + (threadIdx.x >> 6);
+    if (i >= M) return;                                       // whole wave
+    const int64_t p0 = view_offsets[i], p1 = view_offsets[i + 1];
+    double* o = out + 3 * i;
+    if (p1 <= p0) {
+        if (lane == 0) { o[0] = 0.0; o[1] = __builtin_nan(""); o[2] = 0.0; }
+        return;
+    }
+    Shared<MODEL, T> sp;
+    sp.load(P);
+    T vc[12];                                                 // R, t of the view (compact index of its first point)
+    {
+        const T* src = VC + (int64_t)pt_view[p0] * kViewStride;
+#pragma unroll
+        for (int j = 0; j < 12; ++j) vc[j] = src[j];
+    }
+    double s = 0.0, mx = 0.0;
+    for (int64_t p = p0 + lane; p < p1; p += 64) {
+        const T2 m = uv[p];
+        const T2 xy = XY[p];
+        const T z = Z[p];
+        T u, v;
+        project_point<MODEL, T>(sp, vc, xy.x, xy.y, z, u, v);
+        const T ru = m.x - u, rv = m.y - v;
+        const double e = (double)ru * (double)ru + (double)rv * (double)rv;
+        s += e;
+        mx = fmax(mx, e);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        s += __shfl_down(s, off, 64);
+        mx = fmax(mx, __shfl_down(mx, off, 64));
+    }
+    if (lane == 0) {
+        o[0] = s;
+        o[1] = sqrt(s / (double)(p1 - p0));
+        o[2] = sqrt(mx);
+    }
+}
+
+// ---------------------------------------------------------------- per-view covariance blocks
+// calib_cov_finish, after a lambda = 0 round left the views' records [E^T | V] behind and the host inverted the
+// reduced L x L system: with Css = sigma2 S_free^-1 (L x L, zero rows / columns for fixed parameters) and
+// Y = V^-1 E^T (6 x L),
+//   C_vv = sigma2 V^-1 + Y Css Y^T  (6 x 6),     C_sv = -Css Y^T  (L x 6, only when asked for).
+// One LANE per view, as update_backsub_lane_kernel: the lane gathers its view's record(s) itself (its own 128-byte
+// lines), factors V once (cholesky6 at lambda = 0) and substitutes the L columns of E^T and the six unit vectors
+// through the factor. Css and sigma2 are wave-uniform (scalar loads). Row c of Css Y^T is formed, written (cross
+// block) and folded into the lower triangle of C_vv at once, so Y (6 L values) is the only large thing a lane holds.
+// A pivot that is not positive raises *singular and the view writes nothing: the host turns the flag into
+// CALIB_E_SINGULAR. HBM-bound: 768 B in (1536 B with an overflow record), 288 B (+ 48 L B) out per view.
+template <int L, bool STREAM>
+__global__ __launch_bounds__(kSchurThreads) void covariance_views_kernel(
+        const double* __restrict__ G, const int* __restrict__ view_item0, const int* __restrict__ view_ext, int nv,
+        StreamMap sm, const double* __restrict__ Css, double sigma2, double* __restrict__ cov_views /* (M,6,6) */,
+        double* __restrict__ cov_cross /* (M,L,6) or null */, int* __restrict__ singular) {
+    for (int v = blockIdx.x * kSchurThreads + threadIdx.x; v < nv; v += gridDim.x * kSchurThreads) {
+        double V[21], Y[6][L];
+#pragma unroll
+        for (int i = 0; i < 21; ++i) V[i] = 0.0;
+#pragma unroll
+        for (int m = 0; m < 6; ++m) {
+#pragma unroll
+            for (int j = 0; j < L; ++j) Y[m][j] = 0.0;
+        }
+        // one record: rows m = 0..5 of [E^T | V]
+        auto addRecord = [&](const double* __restrict__ g) {
+#pragma unroll
+            for (int m = 0; m < 6; ++m) {
+                const double2* row = reinterpret_cast<const double2*>(g + kGRows + m * 16);
+                double r[16];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) { const double2 t = row[q]; r[2 * q] = t.x; r[2 * q + 1] = t.y; }
+#pragma unroll
+                for (int j = 0; j < L; ++j) Y[m][j] += r[j];
+#pragma unroll
+                for (int n = 0; n <= m; ++n) V[tri(m, n)] += r[L + n];
+            }
+        };
+        const ViewSpan s = view_span<STREAM>(view_item0, sm, v);
+        for (int it = s.i0; it < s.i0 + s.nitems; ++it) addRecord(G + (int64_t)it * kGStride);
+        if (s.extra >= 0) addRecord(G + (int64_t)s.extra * kGStride);
+        double invd[6];
+        if (!cholesky6(V, 0.0, invd)) {
+            *singular = 1;
+            continue;
+        }
+        // Y = V^-1 E^T, column by column, in place
+#pragma unroll
+        for (int j = 0; j < L; ++j) {
+            double b[6], z[6], y[6];
+#pragma unroll
+            for (int m = 0; m < 6; ++m) b[m] = Y[m][j];
+            forward6(V, invd, b, z);
+            backward6(V, invd, z, y);
+#pragma unroll
+            for (int m = 0; m < 6; ++m) Y[m][j] = y[m];
+        }
+        // lower triangle of C_vv, starting from sigma2 V^-1 (column n of V^-1 = the solve of unit vector n)
+        double acc[21];
+#pragma unroll
+        for (int n = 0; n < 6; ++n) {
+            double b[6], z[6], y[6];
+#pragma unroll
+            for (int m = 0; m < 6; ++m) b[m] = m == n ? 1.0 : 0.0;
+            forward6(V, invd, b, z);
+            backward6(V, invd, z, y);
+#pragma unroll
+            for (int m = n; m < 6; ++m) acc[tri(m, n)] = sigma2 * y[m];
+        }
+        const int64_t ext = view_ext[v];
+#pragma unroll
+        for (int c = 0; c < L; ++c) {
+            double t[6];                                      // row c of Css Y^T
+#pragma unroll
+            for (int n = 0; n < 6; ++n) t[n] = 0.0;
+#pragma unroll
+            for (int j = 0; j < L; ++j) {
+                const double cs = Css[c * L + j];
+#pragma unroll
+                for (int n = 0; n < 6; ++n) t[n] = __builtin_fma(cs, Y[n][j], t[n]);
+            }
+            if (cov_cross) {
+                double* dst = cov_cross + (ext * L + c) * 6;
+#pragma unroll
+                for (int n = 0; n < 6; ++n) dst[n] = 0.0 - t[n];
+            }
+#pragma unroll
+            for (int m = 0; m < 6; ++m) {
+#pragma unroll
+                for (int n = 0; n <= m; ++n) acc[tri(m, n)] = __builtin_fma(Y[m][c], t[n], acc[tri(m, n)]);
+            }
+        }
+        double* dst = cov_views + ext * 36;
+#pragma unroll
+        for (int m = 0; m < 6; ++m) {
+#pragma unroll
+            for (int n = 0; n < 6; ++n) dst[m * 6 + n] = m >= n ? acc[tri(m, n)] : acc[tri(n, m)];
+        }
+    }
+}
+
 }  // namespace calib

@@ -272,7 +272,8 @@ def _agreeOnFixedMask(dist, torch, mask, err, device):
 
 
 def refineDistributed(modelName, P0, viewOffsets, sensorPoints, modelPoints, maxIters, dtype="f64",
-                      checkEvery=8, engineFactory=None, allReduceFactory=None, fixedShared=(), **lmOptions):
+                      checkEvery=8, engineFactory=None, allReduceFactory=None, fixedShared=(), uncertainty=False,
+                      **lmOptions):
     """Refine ONE global problem with the views sharded over the ranks of the default
     torch.distributed process group (every rank passes the same global arrays and gets the same
     global result back). -> (sse, P (K,), iters, trace)
@@ -284,7 +285,13 @@ def refineDistributed(modelName, P0, viewOffsets, sensorPoints, modelPoints, max
     fixedShared: shared parameters held fixed, as Calibrator.setFixed takes them (names, aliases, a mapping
     name -> value, or a mask). Every rank must pass the same; the ranks check that they agree and raise together if
     not. An engine made by engineFactory receives the mask through its setFixedShared method; one without that
-    method cannot take a non-empty mask (TypeError)."""
+    method cannot take a non-empty mask (TypeError).
+
+    uncertainty=True: after the loop every rank runs covLocal at the result, the SAME all-reduce the LM rounds used, and
+    covFinish with the global totals (include/calib_lm.h: calib_cov_*), and the result gains a fifth element, a dict
+    with sigma2, dof, covShared (L,L) -- bitwise equal on every rank: it is host arithmetic on the all-reduced
+    buffer --, covViews (M,6,6) and std (K,) in GLOBAL view order, gathered like the extrinsics. The shard engine
+    needs covLocal / covFinish. The default leaves the result and the traffic exactly as they were."""
     import os
     import torch
     import torch.distributed as dist
@@ -364,6 +371,42 @@ def refineDistributed(modelName, P0, viewOffsets, sensorPoints, modelPoints, max
     P[:L] = Plocal[:L]
     for (v0, v1), ext in gathered:
         P[L + 6 * v0:L + 6 * v1] = ext
+    unc = None
+    if uncertainty:
+        unc = _shardedUncertainty(dist, torch, eng, allReduce, onGpu, okDevice, Plocal, L, parts, rank, world,
+                                  int(np.asarray(viewOffsets)[-1]), len(viewOffsets) - 1)
     if hasattr(eng, "close"):
         eng.close()
+    if uncertainty:
+        return sse, P, iters, trace, unc
     return sse, P, iters, trace
+
+
+def _shardedUncertainty(dist, torch, eng, allReduce, onGpu, okDevice, Plocal, L, parts, rank, world, totalPoints,
+                        totalViews):
+    """covLocal -> the run's all-reduce -> covFinish on every rank, then the pose blocks in global view order"""
+    err = None
+    try:
+        if getattr(allReduce, "kind", "") == "peer":
+            # the peer exchange lives inside the LM rounds' reduce kernel; this one sum rides on torch.distributed
+            allReduce = torchAllReduce(eng, torch.device("cuda", eng.device))
+        eng.covLocal(Plocal)
+    except Exception as e:           # noqa: BLE001 -- re-raised below, after every rank knows
+        err = e
+    _raiseTogether(dist, torch, err, okDevice)
+    allReduce()
+    res = None
+    try:
+        res = eng.covFinish(totalPoints, totalViews)
+    except Exception as e:           # noqa: BLE001
+        err = e
+    _raiseTogether(dist, torch, err, okDevice)
+    gathered = [None] * world
+    dist.all_gather_object(gathered, (parts[rank], res["covViews"], res["std"][L:]))
+    covViews = np.empty((totalViews, 6, 6))
+    std = np.empty(L + 6 * totalViews)
+    std[:L] = res["std"][:L]
+    for (v0, v1), cv, sd in gathered:
+        covViews[v0:v1] = cv
+        std[L + 6 * v0:L + 6 * v1] = sd
+    return {"sigma2": res["sigma2"], "dof": res["dof"], "covShared": res["covShared"], "covViews": covViews, "std": std}

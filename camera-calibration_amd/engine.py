@@ -387,6 +387,50 @@ class RefineEngine:
                                          nat.dptr(trace)))
         return sse.value, P, iters.value, trace[:iters.value]
 
+    # ---- uncertainty (include/calib_lm.h: calib_view_errors, calib_cov_*) ----------------------
+    def viewErrors(self, P):
+        """Per-view reprojection errors at P -> dict sse (M,) = sum |r|^2, rms (M,) = sqrt(sse / n_i) (NaN for an
+        empty view), max (M,) = largest point error of the view. One kernel; nothing comes back per point."""
+        P = self._P(P)
+        sse, rms, mx = np.empty(self.M), np.empty(self.M), np.empty(self.M)
+        nat.check(self._lib.calib_view_errors(self._h, nat.dptr(P), nat.dptr(sse), nat.dptr(rms), nat.dptr(mx)))
+        return {"sse": sse, "rms": rms, "max": mx}
+
+    def _covOutputs(self, wantViews, wantCross):
+        return (np.empty((self.L, self.L)), np.empty((self.M, 6, 6)) if wantViews else None,
+                np.empty((self.M, self.L, 6)) if wantCross else None, np.empty(self.K))
+
+    @staticmethod
+    def _covResult(sigma2, dof, outs):
+        return {"sigma2": sigma2.value, "dof": dof.value, "covShared": outs[0], "covViews": outs[1],
+                "covCross": outs[2], "std": outs[3]}
+
+    def covariance(self, P, wantViews=True, wantCross=False):
+        """Covariance of the estimate at P, sigma2 (Jf^T Jf)^-1 through the block-arrow structure (calib_covariance)
+        -> dict sigma2, dof, covShared (L,L), covViews (M,6,6) | None, covCross (M,L,6) | None, std (K,). Fixed
+        shared parameters (setFixedShared) have zero rows and columns. Pose entries are in the units of P: Euler
+        angles in DEGREES, then t."""
+        P = self._P(P)
+        outs = self._covOutputs(wantViews, wantCross)
+        sigma2, dof = ctypes.c_double(0.0), ctypes.c_int64(0)
+        nat.check(self._lib.calib_covariance(self._h, nat.dptr(P), ctypes.byref(sigma2), ctypes.byref(dof),
+                                             *(nat.dptr(o) for o in outs)))
+        return self._covResult(sigma2, dof, outs)
+
+    def covLocal(self, P):
+        """stepping form, for shards: enqueue the lambda = 0 round at P; the reduce buffer then holds this shard's
+        sums, to be all-reduced before covFinish"""
+        nat.check(self._lib.calib_cov_local(self._h, nat.dptr(self._P(P))))
+
+    def covFinish(self, totalPoints, totalViews, wantViews=True, wantCross=False):
+        """-> the dict of covariance(), from the all-reduced buffer and the GLOBAL totals; covViews / covCross / std
+        cover this shard's views"""
+        outs = self._covOutputs(wantViews, wantCross)
+        sigma2, dof = ctypes.c_double(0.0), ctypes.c_int64(0)
+        nat.check(self._lib.calib_cov_finish(self._h, int(totalPoints), int(totalViews), ctypes.byref(sigma2),
+                                             ctypes.byref(dof), *(nat.dptr(o) for o in outs)))
+        return self._covResult(sigma2, dof, outs)
+
     # ---- profiling -----------------------------------------------------------------------
     def profileEnable(self, on=True, every=1):
         """HIP-event timing of the dominant kernels; every = N times only every N-th launch of each

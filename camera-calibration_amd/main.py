@@ -27,6 +27,17 @@ def calibrateCamera(allDetections: list, distortionType: str, maxIters, **engine
     return calibrate.Calibrator(modelClass(), **engineOptions).calibrate(allDetections, maxIters)
 
 
+def calibrateCameraExtended(allDetections: list, distortionType: str, maxIters, **engineOptions) -> tuple:
+    """calibrateCamera plus the uncertainty of its result: (sse, A, W, k, uncertainty) with the first four exactly
+    as calibrateCamera returns them and the fifth a uncertainty.CalibrationUncertainty (standard deviations and
+    covariance of the parameters, per-view reprojection errors), computed on the GPU."""
+    try:
+        modelClass = _MODELS[distortionType]
+    except KeyError:
+        raise ValueError(f"Distortion type: {distortionType} unknown") from None
+    return calibrate.Calibrator(modelClass(), **engineOptions).calibrateExtended(allDetections, maxIters)
+
+
 def estimatePoses(allDetections: list, distortionType: str, A, k, maxIters=20, **engineOptions) -> tuple:
     """Board poses of detections taken with a KNOWN camera (A (3,3), k): closed-form start, then the per-view
     pose-only refinement on the GPU. Returns (ssePerView (M,), W list of (4,4), iters (M,), status (M,))."""

@@ -242,6 +242,42 @@ int calib_lm_peek_trace(calib_handle_t h, int iter, double* out_row, int* out_it
 int calib_lm_end(calib_handle_t h, double* P_out, double* out_sse, int* out_iters,
                  double* out_trace);
 
+/* ---- uncertainty of an estimate: per-view reprojection errors and the parameter covariance -----------------
+ * Surface beside the drop-in one (the reference returns neither). Evaluated at a parameter vector P, normally the
+ * refinement's result. With n the total number of points, r the (n,2) residuals at P, F the fixed shared
+ * parameters of the handle (calib_set_fixed_shared), Jf the Jacobian with the columns in F deleted and
+ * K_free = L - |F| + 6 M:
+ *   dof = 2 n - K_free (dof <= 0: CALIB_E_INVALID),   sigma2 = sse(P) / dof,   C = sigma2 (Jf^T Jf)^-1
+ * -- no damping, no pseudo-inverse; rows and columns of fixed parameters are exactly 0.0 in every output. C is never
+ * formed densely: with S the Schur complement of the shared block, V_i / E_i view i's blocks and Y_i = V_i^-1 E_i^T,
+ *   C_ss = sigma2 S_free^-1,   C_vv,i = sigma2 V_i^-1 + Y_i C_ss Y_i^T,   C_sv,i = -C_ss Y_i^T.
+ * A view whose V_i has a pivot that is not positive (e.g. fewer than three points), or an S_free that has one, is
+ * CALIB_E_SINGULAR: the condition under which the LM step fails. The blocks come from one LM round at lambda = 0 in the
+ * handle's LM mode and storage type (fp32 storage: the Jacobian the fp32 path evaluates; sums and all that follows
+ * are fp64). UNITS: pose parameters are those of P -- Euler angles in DEGREES, then t -- and standard deviations and
+ * covariances are of those quantities. Sums are fixed-order: results are bitwise reproducible for a given shard, mode
+ * and device.
+ *
+ * calib_view_errors: for view i with n_i points, view_sse = sum |r|^2, view_rms = sqrt(view_sse / n_i) (per-point RMS;
+ *   NaN for an empty view), view_max = max |r| (0 for an empty view). Each output (M) or NULL. One kernel, nothing is
+ *   written per point. CALIB_E_STATE while a stepping LM run is active (it owns the view constants).
+ * calib_cov_local: enqueues the lambda = 0 round at P; the handle's reduce buffer (calib_lm_bind_reduce_buffer) then
+ *   holds this shard's sums. Sharded: all-reduce that buffer by any carrier (calib_lm_allreduce is the library's),
+ *   then every rank calls
+ * calib_cov_finish with the GLOBAL totals: the L x L step is host arithmetic on the all-reduced buffer, so
+ *   out_cov_shared is bitwise equal on every rank. out_cov_views (M,6,6) and out_cov_cross (M,L,6) are this shard's
+ *   views; out_std (K, the shard's K) = sqrt of the diagonal. Any output may be NULL.
+ * calib_covariance = calib_cov_local + calib_cov_finish with the handle's own totals (single shard).
+ * All three calib_cov_* calls return CALIB_E_STATE while a stepping LM run is active on the handle. */
+int calib_view_errors(calib_handle_t h, const double* P,
+                      double* out_view_sse, double* out_view_rms, double* out_view_max);
+int calib_cov_local(calib_handle_t h, const double* P);
+int calib_cov_finish(calib_handle_t h, int64_t total_points, int64_t total_views,
+                     double* out_sigma2, int64_t* out_dof,
+                     double* out_cov_shared, double* out_cov_views, double* out_cov_cross, double* out_std);
+int calib_covariance(calib_handle_t h, const double* P, double* out_sigma2, int64_t* out_dof,
+                     double* out_cov_shared, double* out_cov_views, double* out_cov_cross, double* out_std);
+
 /* Numeric forward model on caller points (no problem needed):
  *   calib_distort_points            DistortionModel.distortPoints          src/distortion.py:78-108,198-220
  *   calib_project_with_distortion   DistortionModel.projectWithDistortion  src/distortion.py:42-59
