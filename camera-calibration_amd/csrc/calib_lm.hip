@@ -4,6 +4,7 @@
 #include "kernels.hpp"
 #include "host_rows.hpp"
 #include "launch_plan.hpp"
+#include "shard_layout.hpp"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -78,9 +79,10 @@ struct DevBuf {
         if (count <= n && p) return hipSuccess;
         release();
         if (count == 0) return hipSuccess;
-        hipError_t e = hipMalloc((void**)&p, count * sizeof(U));
-        if (e == hipSuccess) n = count;
-        return e;
+        const hipError_t e = hipMalloc((void**)&p, count * sizeof(U));
+        if (e != hipSuccess) return e;
+        n = count;
+        return hipSuccess;
     }
     void release() {
         if (p) (void)hipFree(p);
@@ -120,12 +122,17 @@ struct calib_handle_s {
     int uniform_n = 0;            // > 0: every item is one whole view of exactly this many points, in order (item i = view i = points [i n, (i+1) n))
     Knobs knobs;                  // CALIB_* tuning variables (calib_create)
     LaunchPlan plan;              // kernel forms and grids of this problem's LM rounds (plan_of)
-    // LM rounds walk the points in chunks of whole views so that a chunk's compact J
-    // (written by the jacobian kernel, read once by the gram kernel) can stay on-die
-    struct Chunk { int64_t p0, p1; int item0, item1; };
-    std::vector<Chunk> chunks;
+    std::vector<ShardChunk> chunks;   // of the two-kernel rounds (shard_layout.hpp)
     int64_t max_chunk_points = 0;
-    DevBuf<unsigned char> uv, XY, Z, VC, J, r, y;   // typed by dtype
+    DevBuf<unsigned char> uv, XY, Z, VC, J, r, y;   // typed by dtype: the launches read them through the accessors
+    template <typename U> static U* as(const DevBuf<unsigned char>& b) { return reinterpret_cast<U*>(b.p); }
+    template <typename U> U* uv_as() const { return as<U>(uv); }
+    template <typename U> U* XY_as() const { return as<U>(XY); }
+    template <typename U> U* Z_as() const { return as<U>(Z); }
+    template <typename U> U* VC_as() const { return as<U>(VC); }
+    template <typename U> U* J_as() const { return as<U>(J); }
+    template <typename U> U* r_as() const { return as<U>(r); }
+    template <typename U> U* y_as() const { return as<U>(y); }
     DevBuf<int> pt_view, view_ext, item_n, view_item0, item_view;
     DevBuf<uint32_t> emit_tab;    // fused kernel's record assembly table (buildEmitTable)
     DevBuf<int32_t> stream_ops;   // fused_stream_kernel's per-lane record offsets (buildStreamOps)
@@ -207,6 +214,36 @@ void launch_kind(calib_handle_s* h, int kind, F kernel, dim3 grid, dim3 block, s
         hipLaunchKernelGGL(kernel, grid, block, shmem, h->stream, args...);
 }
 
+calib_handle_s* const kNoHandle = nullptr;      // LAUNCHED of the entry points that take no handle
+
+// ---- form dispatch -----------------------------------------------------------------------
+// A run-time (model, dtype) as compile-time arguments: f is a generic lambda that gets a Form value and reads MODEL,
+// L, C, T and T2 from its type. A launch names only what its kernel takes, so the kernels instantiated are the ones a
+// ladder at the site would spell out -- in the ladders' order (storage type, then model), which keeps the module's
+// kernels, and the numbering of their labels, where they were. The stream form of the per-view kernels (plan.stream())
+// stays a branch at its three sites for the same reason: there it alternates inside a (model, dtype) form.
+static_assert(CALIB_MODEL_RADTAN == kRadtan && CALIB_MODEL_FISHEYE == kFisheye, "the C ABI's model ids are the kernels'");
+template <int MODEL_, typename T_>
+struct Form {
+    static constexpr int MODEL = MODEL_, L = ModelTraits<MODEL_>::L, C = ModelTraits<MODEL_>::C;
+    using T = T_;
+    using T2 = typename Pair<T_>::type;
+};
+
+template <typename F>
+int dispatch(int model, int dtype, F&& f) {
+    auto byModel = [&](auto t) -> int { return model == kRadtan ? f(Form<kRadtan, decltype(t)>{}) : f(Form<kFisheye, decltype(t)>{}); };
+    return dtype == CALIB_DTYPE_F64 ? byModel(double{}) : byModel(float{});
+}
+template <typename F>
+int dispatch(const calib_handle_s* h, F&& f) { return dispatch(h->model, h->dtype, f); }
+// entry points without a handle: fp64, the model alone
+template <typename F>
+int dispatch_model(int model, F&& f) { return dispatch(model, CALIB_DTYPE_F64, f); }
+
+bool known_model(int model) { return model == CALIB_MODEL_RADTAN || model == CALIB_MODEL_FISHEYE; }
+int num_distortion(int model) { return model == CALIB_MODEL_RADTAN ? 5 : 4; }
+
 // ---- RCCL, resolved at run time (calib_rccl_load) ------------------------------------------
 // Only the handful of entry points the one all-reduce needs; types as in rccl.h (ncclUniqueId is 128
 // opaque bytes passed by value, ncclDouble = 8, ncclSum = 0, ncclSuccess = 0).
@@ -261,27 +298,24 @@ int upload_staged(calib_handle_s* h, void* dst, const HostRows& src, size_t byte
         h->stage_ready = true;
     }
     const size_t nchunks = (bytes + kUploadChunk - 1) / kUploadChunk;
+    auto copyShare = [&](int t) -> hipError_t {       // thread t: chunks t, t + kUploadThreads, ...
+        if (hipError_t e = hipSetDevice(h->device)) return e;
+        size_t use = 0;
+        for (size_t c = (size_t)t; c < nchunks; c += kUploadThreads, ++use) {
+            const int b = (int)(use & 1);
+            const size_t off = c * kUploadChunk, n = std::min(kUploadChunk, bytes - off);
+            if (use >= 2)                                                       // this buffer's previous DMA is done
+                if (hipError_t e = hipEventSynchronize(h->stage_ev[t][b])) return e;
+            src.copy(static_cast<char*>(h->stage_buf[t][b]), off, n);
+            if (hipError_t e = hipMemcpyAsync(static_cast<char*>(dst) + off, h->stage_buf[t][b], n, hipMemcpyHostToDevice,
+                                              h->stage_stream[t])) return e;
+            if (hipError_t e = hipEventRecord(h->stage_ev[t][b], h->stage_stream[t])) return e;
+        }
+        return hipStreamSynchronize(h->stage_stream[t]);
+    };
     hipError_t errs[kUploadThreads];
     std::thread workers[kUploadThreads];
-    for (int t = 0; t < kUploadThreads; ++t) {
-        errs[t] = hipSuccess;
-        workers[t] = std::thread([=, &errs, &src]() {
-            hipError_t e = hipSetDevice(h->device);
-            size_t use = 0;
-            for (size_t c = (size_t)t; c < nchunks && e == hipSuccess; c += kUploadThreads, ++use) {
-                const int b = (int)(use & 1);
-                const size_t off = c * kUploadChunk, n = std::min(kUploadChunk, bytes - off);
-                if (use >= 2) e = hipEventSynchronize(h->stage_ev[t][b]);      // this buffer's previous DMA is done
-                if (e != hipSuccess) break;
-                src.copy(static_cast<char*>(h->stage_buf[t][b]), off, n);
-                e = hipMemcpyAsync(static_cast<char*>(dst) + off, h->stage_buf[t][b], n, hipMemcpyHostToDevice,
-                                   h->stage_stream[t]);
-                if (e == hipSuccess) e = hipEventRecord(h->stage_ev[t][b], h->stage_stream[t]);
-            }
-            if (e == hipSuccess) e = hipStreamSynchronize(h->stage_stream[t]);
-            errs[t] = e;
-        });
-    }
+    for (int t = 0; t < kUploadThreads; ++t) workers[t] = std::thread([&errs, &copyShare, t]() { errs[t] = copyShare(t); });
     for (auto& w : workers) w.join();
     for (int t = 0; t < kUploadThreads; ++t)
         if (errs[t] != hipSuccess) return fail(CALIB_E_HIP, std::string("staged upload: ") + hipGetErrorString(errs[t]));
@@ -289,100 +323,61 @@ int upload_staged(calib_handle_s* h, void* dst, const HostRows& src, size_t byte
 }
 
 // ---- launches ---------------------------------------------------------------------------
-template <typename T>
+int launch_jacobian(calib_handle_s* h, const double* P0, const double* P1, const LMState* st, int sel,
+                    bool wantJ, bool wantR, bool wantY, bool wantSse, int64_t p_begin, int64_t p_end) {
+    if (p_end <= p_begin) return CALIB_OK;
+    return dispatch(h, [&](auto form) -> int {
+        using F = decltype(form);
+        using T = typename F::T;
+        using T2 = typename F::T2;
+        JacArgs<T> a;
+        a.P0 = P0; a.P1 = P1; a.st = st; a.sel = sel;
+        a.uv = h->uv_as<const T2>();
+        a.XY = h->XY_as<const T2>();
+        a.Z = h->Z_as<const T>();
+        a.pt_view = h->pt_view.p;
+        a.p_begin = p_begin;
+        a.p_end = p_end;
+        a.VC = h->VC_as<const T>();
+        a.J = wantJ ? h->J_as<T2>() : nullptr;
+        a.r = wantR ? h->r_as<T2>() : nullptr;
+        a.y = wantY ? h->y_as<T2>() : nullptr;
+        a.sse_part = wantSse ? h->sse_part.p : nullptr;
+        const size_t lds = 32 + (size_t)h->max_views_per_tile * kViewStride * sizeof(T);
+        const unsigned tiles = (unsigned)((p_end - p_begin + kTile - 1) / kTile);
+        launch_kind(h, 0, jacobian_kernel<F::MODEL, T>, dim3(tiles), dim3(kTile), lds, a);
+        LAUNCHED(h, "jacobian_kernel");
+        return CALIB_OK;
+    });
+}
+
 int launch_view_setup(calib_handle_s* h, const double* P0, const double* P1, const LMState* st, int sel) {
     if (h->nv == 0) return CALIB_OK;
     const int threads = 64;
     const int blocks = (h->nv + threads - 1) / threads;
-    hipLaunchKernelGGL((view_setup_kernel<T>), dim3(blocks), dim3(threads), 0, h->stream, P0, P1, st, sel,
-                       h->L, h->view_ext.p, h->nv, reinterpret_cast<T*>(h->VC.p));
-    LAUNCHED(h, "view_setup_kernel");
-    return CALIB_OK;
-}
-
-template <int MODEL, typename T>
-int launch_jacobian_t(calib_handle_s* h, const double* P0, const double* P1, const LMState* st, int sel,
-                      bool wantJ, bool wantR, bool wantY, bool wantSse, int64_t p_begin, int64_t p_end) {
-    using T2 = typename Pair<T>::type;
-    if (p_end <= p_begin) return CALIB_OK;
-    JacArgs<T> a;
-    a.P0 = P0; a.P1 = P1; a.st = st; a.sel = sel;
-    a.uv = reinterpret_cast<const T2*>(h->uv.p);
-    a.XY = reinterpret_cast<const T2*>(h->XY.p);
-    a.Z = reinterpret_cast<const T*>(h->Z.p);
-    a.pt_view = h->pt_view.p;
-    a.p_begin = p_begin;
-    a.p_end = p_end;
-    a.VC = reinterpret_cast<const T*>(h->VC.p);
-    a.J = wantJ ? reinterpret_cast<T2*>(h->J.p) : nullptr;
-    a.r = wantR ? reinterpret_cast<T2*>(h->r.p) : nullptr;
-    a.y = wantY ? reinterpret_cast<T2*>(h->y.p) : nullptr;
-    a.sse_part = wantSse ? h->sse_part.p : nullptr;
-    const size_t lds = 32 + (size_t)h->max_views_per_tile * kViewStride * sizeof(T);
-    const unsigned tiles = (unsigned)((p_end - p_begin + kTile - 1) / kTile);
-    launch_kind(h, 0, jacobian_kernel<MODEL, T>, dim3(tiles), dim3(kTile), lds, a);
-    LAUNCHED(h, "jacobian_kernel");
-    return CALIB_OK;
-}
-
-int launch_jacobian(calib_handle_s* h, const double* P0, const double* P1, const LMState* st, int sel,
-                    bool wantJ, bool wantR, bool wantY, bool wantSse, int64_t p_begin, int64_t p_end) {
-    if (h->dtype == CALIB_DTYPE_F64) {
-        return h->model == CALIB_MODEL_RADTAN
-                   ? launch_jacobian_t<kRadtan, double>(h, P0, P1, st, sel, wantJ, wantR, wantY, wantSse, p_begin, p_end)
-                   : launch_jacobian_t<kFisheye, double>(h, P0, P1, st, sel, wantJ, wantR, wantY, wantSse, p_begin, p_end);
-    }
-    return h->model == CALIB_MODEL_RADTAN
-               ? launch_jacobian_t<kRadtan, float>(h, P0, P1, st, sel, wantJ, wantR, wantY, wantSse, p_begin, p_end)
-               : launch_jacobian_t<kFisheye, float>(h, P0, P1, st, sel, wantJ, wantR, wantY, wantSse, p_begin, p_end);
-}
-
-int launch_view_setup_any(calib_handle_s* h, const double* P0, const double* P1, const LMState* st, int sel) {
-    return h->dtype == CALIB_DTYPE_F64 ? launch_view_setup<double>(h, P0, P1, st, sel)
-                                       : launch_view_setup<float>(h, P0, P1, st, sel);
-}
-
-template <typename T, int C>
-int launch_gram_t(calib_handle_s* h, const LMState* st, int sel, int item0, int item1, int64_t origin) {
-    using T2 = typename Pair<T>::type;
-    if (item1 <= item0) return CALIB_OK;
-    const int ipb = 4 / h->plan.gram_wpi;  // items per workgroup
-    const int blocks = (item1 - item0 + ipb - 1) / ipb;
-    launch_kind(h, 1, gram_kernel<T, C>, dim3(blocks), dim3(256), 0,
-                reinterpret_cast<const T2*>(h->J.p), reinterpret_cast<const T2*>(h->r.p),
-                (const int64_t*)h->item_pt0.p, (const int*)h->item_n.p, item0, item1, origin, h->plan.gram_wpi, st, sel, h->G[0].p,
-                h->G[1].p, h->bpart.p, h->n_bpart);
-    h->n_bpart += blocks;                  // the chunk's workgroups append their partials
-    LAUNCHED(h, "gram_kernel");
-    return CALIB_OK;
+    return dispatch(h, [&](auto form) -> int {
+        using T = typename decltype(form)::T;
+        hipLaunchKernelGGL((view_setup_kernel<T>), dim3(blocks), dim3(threads), 0, h->stream, P0, P1, st, sel,
+                           h->L, h->view_ext.p, h->nv, h->VC_as<T>());
+        LAUNCHED(h, "view_setup_kernel");
+        return CALIB_OK;
+    });
 }
 
 int launch_gram(calib_handle_s* h, const LMState* st, int sel, int item0, int item1, int64_t origin) {
-    if (h->dtype == CALIB_DTYPE_F64)
-        return h->model == CALIB_MODEL_RADTAN ? launch_gram_t<double, 16>(h, st, sel, item0, item1, origin)
-                                              : launch_gram_t<double, 15>(h, st, sel, item0, item1, origin);
-    return h->model == CALIB_MODEL_RADTAN ? launch_gram_t<float, 16>(h, st, sel, item0, item1, origin)
-                                          : launch_gram_t<float, 15>(h, st, sel, item0, item1, origin);
-}
-
-template <int MODEL, typename T>
-int launch_fused_t(calib_handle_s* h, const LMState* st, int sel) {
-    using T2 = typename Pair<T>::type;
-    const LaunchPlan& p = h->plan;
-    if (p.fused_blocks == 0) return CALIB_OK;
-    auto launch = [&](auto kernel) {
-        launch_kind(h, 2, kernel, dim3(p.fused_blocks), dim3(256), 0, (const double*)h->P[0].p,
-                    (const double*)h->P[1].p, reinterpret_cast<const T2*>(h->uv.p), reinterpret_cast<const T2*>(h->XY.p),
-                    reinterpret_cast<const T*>(h->Z.p), reinterpret_cast<const T*>(h->VC.p), (const int64_t*)h->item_pt0.p,
-                    (const int*)h->item_n.p, (const int*)h->item_view.p, h->n_items, h->uniform_n, p.ipw, p.fused_wpi,
-                    (const uint32_t*)h->emit_tab.p, st, sel, h->G[0].p, h->G[1].p, h->bpart.p);
-    };
-    if (p.fused == FusedForm::Tile) launch(fused_kernel<MODEL, T, false, false>);
-    else if (p.fused == FusedForm::TileMulti) launch(fused_kernel<MODEL, T, false, true>);
-    else if constexpr (sizeof(T) == 8) launch(fused_kernel<MODEL, T, true, false>);    // Block44: fp64 only
-    h->n_bpart = p.fused_blocks;
-    LAUNCHED(h, "fused_kernel");
-    return CALIB_OK;
+    if (item1 <= item0) return CALIB_OK;
+    const int ipb = 4 / h->plan.gram_wpi;  // items per workgroup
+    const int blocks = (item1 - item0 + ipb - 1) / ipb;
+    return dispatch(h, [&](auto form) -> int {
+        using F = decltype(form);
+        using T2 = typename F::T2;
+        launch_kind(h, 1, gram_kernel<typename F::T, F::C>, dim3(blocks), dim3(256), 0, h->J_as<const T2>(), h->r_as<const T2>(),
+                    (const int64_t*)h->item_pt0.p, (const int*)h->item_n.p, item0, item1, origin, h->plan.gram_wpi, st, sel, h->G[0].p,
+                    h->G[1].p, h->bpart.p, h->n_bpart);
+        h->n_bpart += blocks;                  // the chunk's workgroups append their partials
+        LAUNCHED(h, "gram_kernel");
+        return CALIB_OK;
+    });
 }
 
 // records of this problem's fused rounds: stream form (view records + one overflow record per wave) or one per item
@@ -395,28 +390,37 @@ StreamMap stream_map(const calib_handle_s* h) {
 }
 int num_records(const calib_handle_s* h) { return std::max(h->n_items, 1) + h->plan.stream_waves; }
 
-template <int MODEL>
-int launch_fused_stream(calib_handle_s* h, const LMState* st, int sel) {
-    const LaunchPlan& p = h->plan;
-    launch_kind(h, 2, fused_stream_kernel<MODEL>, dim3(p.fused_blocks), dim3(256), 0, (const double*)h->P[0].p, (const double*)h->P[1].p,
-                reinterpret_cast<const double2*>(h->uv.p), reinterpret_cast<const double2*>(h->XY.p),
-                reinterpret_cast<const double*>(h->Z.p), reinterpret_cast<const double*>(h->VC.p), h->uniform_n,
-                h->nv, p.stream_share, (const uint32_t*)h->emit_tab.p, (const int32_t*)h->stream_ops.p, st, sel, h->G[0].p, h->G[1].p,
-                h->bpart.p);
-    h->n_bpart = p.fused_blocks;
-    LAUNCHED(h, "fused_stream_kernel");
-    return CALIB_OK;
-}
-
 int launch_fused(calib_handle_s* h, const LMState* st, int sel) {
-    if (h->plan.fused == FusedForm::Stream)
-        return h->model == CALIB_MODEL_RADTAN ? launch_fused_stream<kRadtan>(h, st, sel)
-                                              : launch_fused_stream<kFisheye>(h, st, sel);
-    if (h->dtype == CALIB_DTYPE_F64)
-        return h->model == CALIB_MODEL_RADTAN ? launch_fused_t<kRadtan, double>(h, st, sel)
-                                              : launch_fused_t<kFisheye, double>(h, st, sel);
-    return h->model == CALIB_MODEL_RADTAN ? launch_fused_t<kRadtan, float>(h, st, sel)
-                                          : launch_fused_t<kFisheye, float>(h, st, sel);
+    const LaunchPlan& p = h->plan;
+    if (p.fused == FusedForm::Stream)           // fp64 only (makePlan)
+        return dispatch(h, [&](auto form) -> int {
+            launch_kind(h, 2, fused_stream_kernel<decltype(form)::MODEL>, dim3(p.fused_blocks), dim3(256), 0,
+                        (const double*)h->P[0].p, (const double*)h->P[1].p, h->uv_as<const double2>(), h->XY_as<const double2>(),
+                        h->Z_as<const double>(), h->VC_as<const double>(), h->uniform_n, h->nv, p.stream_share,
+                        (const uint32_t*)h->emit_tab.p, (const int32_t*)h->stream_ops.p, st, sel, h->G[0].p, h->G[1].p, h->bpart.p);
+            h->n_bpart = p.fused_blocks;
+            LAUNCHED(h, "fused_stream_kernel");
+            return CALIB_OK;
+        });
+    if (p.fused_blocks == 0) return CALIB_OK;
+    return dispatch(h, [&](auto form) -> int {
+        using F = decltype(form);
+        using T = typename F::T;
+        using T2 = typename F::T2;
+        auto launch = [&](auto kernel) {
+            launch_kind(h, 2, kernel, dim3(p.fused_blocks), dim3(256), 0, (const double*)h->P[0].p, (const double*)h->P[1].p,
+                        h->uv_as<const T2>(), h->XY_as<const T2>(), h->Z_as<const T>(), h->VC_as<const T>(),
+                        (const int64_t*)h->item_pt0.p, (const int*)h->item_n.p, (const int*)h->item_view.p, h->n_items,
+                        h->uniform_n, p.ipw, p.fused_wpi, (const uint32_t*)h->emit_tab.p, st, sel, h->G[0].p, h->G[1].p,
+                        h->bpart.p);
+        };
+        if (p.fused == FusedForm::Tile) launch(fused_kernel<F::MODEL, T, false, false>);
+        else if (p.fused == FusedForm::TileMulti) launch(fused_kernel<F::MODEL, T, false, true>);
+        else if constexpr (sizeof(T) == 8) launch(fused_kernel<F::MODEL, T, true, false>);    // Block44: fp64 only
+        h->n_bpart = p.fused_blocks;
+        LAUNCHED(h, "fused_kernel");
+        return CALIB_OK;
+    });
 }
 
 // per-view kernels skip the view -> item indirection when every view is a single item
@@ -439,19 +443,17 @@ PeerExchange next_exchange(calib_handle_s* h) {
 
 int launch_schur(calib_handle_s* h, const LMState* st) {
     const LaunchPlan& p = h->plan;
-    dim3 grid(p.schur_blocks, 3);
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, grid, dim3(kSchurBlock), 0, h->stream, h->G[0].p, h->G[1].p, st, view_items(h), h->nv,
-                           stream_map(h), h->bpart.p, h->n_bpart, h->part.p);
-    };
-    auto pick = [&](auto Lc) {
-        constexpr int LL = decltype(Lc)::value;
-        if (p.stream()) { if (p.wide_heads) launch(schur_kernel<LL, true, true>); else launch(schur_kernel<LL, false, true>); }
-        else { if (p.wide_heads) launch(schur_kernel<LL, true, false>); else launch(schur_kernel<LL, false, false>); }
-    };
-    if (h->L == 10) pick(std::integral_constant<int, 10>{}); else pick(std::integral_constant<int, 9>{});
-    LAUNCHED(h, "schur_kernel");
-    return CALIB_OK;
+    return dispatch(h, [&](auto form) -> int {
+        using F = decltype(form);
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(p.schur_blocks, 3), dim3(kSchurBlock), 0, h->stream, h->G[0].p, h->G[1].p, st,
+                               view_items(h), h->nv, stream_map(h), h->bpart.p, h->n_bpart, h->part.p);
+        };
+        if (p.stream()) { if (p.wide_heads) launch(schur_kernel<F::L, true, true>); else launch(schur_kernel<F::L, false, true>); }
+        else { if (p.wide_heads) launch(schur_kernel<F::L, true, false>); else launch(schur_kernel<F::L, false, false>); }
+        LAUNCHED(h, "schur_kernel");
+        return CALIB_OK;
+    });
 }
 
 int launch_schur_reduce(calib_handle_s* h, const LMState* st, double* red) {
@@ -472,39 +474,37 @@ int launch_schur_reduce(calib_handle_s* h, const LMState* st, double* red) {
 LMState* st_cur(calib_handle_s* h) { return h->st.p + (h->rounds_enqueued & 1); }
 LMState* st_next(calib_handle_s* h) { return h->st.p + ((h->rounds_enqueued + 1) & 1); }
 
-template <int L, typename T>
-int launch_update_backsub_t(calib_handle_s* h) {
-    const LaunchPlan& p = h->plan;
-    UpdArgs<T> a;
-    a.G0 = h->G[0].p; a.G1 = h->G[1].p;
-    a.st_in = st_cur(h); a.st_out = st_next(h);
-    a.red = h->red;
-    a.view_item0 = view_items(h);
-    a.view_ext = h->view_ext.p;
-    a.nv = h->nv;
-    a.sm = stream_map(h);
-    a.P0 = h->P[0].p; a.P1 = h->P[1].p;
-    a.trace = h->trace.p;
-    a.VC = reinterpret_cast<T*>(h->VC.p);
-    auto launch = [&](auto kernel, int threads, const char* name) -> int {
-        hipLaunchKernelGGL(kernel, dim3(p.update_blocks), dim3(threads), 0, h->stream, a);
-        LAUNCHED(h, name);
-        return CALIB_OK;
-    };
-    if (p.update == UpdateForm::Small)
-        return p.stream() ? launch(update_backsub_small_kernel<L, T, true>, kUpdThreads, "update_backsub_small_kernel")
-                          : launch(update_backsub_small_kernel<L, T, false>, kUpdThreads, "update_backsub_small_kernel");
-    if (p.update == UpdateForm::Lane)
-        return p.stream() ? launch(update_backsub_lane_kernel<L, T, true>, kSchurThreads, "update_backsub_lane_kernel")
-                          : launch(update_backsub_lane_kernel<L, T, false>, kSchurThreads, "update_backsub_lane_kernel");
-    return p.stream() ? launch(update_backsub_kernel<L, T, true>, kSchurThreads, "update_backsub_kernel")
-                      : launch(update_backsub_kernel<L, T, false>, kSchurThreads, "update_backsub_kernel");
-}
-
 int launch_update_backsub(calib_handle_s* h) {
-    if (h->dtype == CALIB_DTYPE_F64)
-        return h->L == 10 ? launch_update_backsub_t<10, double>(h) : launch_update_backsub_t<9, double>(h);
-    return h->L == 10 ? launch_update_backsub_t<10, float>(h) : launch_update_backsub_t<9, float>(h);
+    const LaunchPlan& p = h->plan;
+    return dispatch(h, [&](auto form) -> int {
+        using F = decltype(form);
+        using T = typename F::T;
+        UpdArgs<T> a;
+        a.G0 = h->G[0].p; a.G1 = h->G[1].p;
+        a.st_in = st_cur(h); a.st_out = st_next(h);
+        a.red = h->red;
+        a.view_item0 = view_items(h);
+        a.view_ext = h->view_ext.p;
+        a.nv = h->nv;
+        a.sm = stream_map(h);
+        a.P0 = h->P[0].p; a.P1 = h->P[1].p;
+        a.trace = h->trace.p;
+        a.VC = h->VC_as<T>();
+        auto launch = [&](auto kernel, int threads, const char* name) -> int {
+            hipLaunchKernelGGL(kernel, dim3(p.update_blocks), dim3(threads), 0, h->stream, a);
+            LAUNCHED(h, name);
+            return CALIB_OK;
+        };
+        constexpr int L = F::L;
+        if (p.update == UpdateForm::Small)
+            return p.stream() ? launch(update_backsub_small_kernel<L, T, true>, kUpdThreads, "update_backsub_small_kernel")
+                              : launch(update_backsub_small_kernel<L, T, false>, kUpdThreads, "update_backsub_small_kernel");
+        if (p.update == UpdateForm::Lane)
+            return p.stream() ? launch(update_backsub_lane_kernel<L, T, true>, kSchurThreads, "update_backsub_lane_kernel")
+                              : launch(update_backsub_lane_kernel<L, T, false>, kSchurThreads, "update_backsub_lane_kernel");
+        return p.stream() ? launch(update_backsub_kernel<L, T, true>, kSchurThreads, "update_backsub_kernel")
+                          : launch(update_backsub_kernel<L, T, false>, kSchurThreads, "update_backsub_kernel");
+    });
 }
 
 LaunchPlan plan_of(const calib_handle_s* h) {
@@ -520,89 +520,139 @@ int need_problem(calib_handle_s* h) {
 
 int64_t numParams(const calib_handle_s* h) { return h->L + 6 * h->M; }
 
-}  // namespace
-
-// ============================================================================ C-ABI
-extern "C" {
-
-int calib_version(void) { return 420; }   // 4.2: calib_view_errors, calib_cov_local / calib_cov_finish / calib_covariance
-
-const char* calib_last_error(void) { return g_err.c_str(); }
-
-int calib_device_count(int* out_count) {
-    if (!out_count) return fail(CALIB_E_INVALID, "out_count is null");
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess) {
-        *out_count = 0;
-        return fail(CALIB_E_HIP, std::string("hipGetDeviceCount: ") + hipGetErrorString(e));
+// ---- calib_set_problem -------------------------------------------------------------------
+// CALIB_TIMING: stage times of calib_set_problem on stderr
+struct Laps {
+    bool on;
+    double mark = now();
+    static double now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+    void operator()(const char* what) {
+        if (!on) return;
+        const double t = now();
+        std::fprintf(stderr, "  set_problem %-28s %.3f ms\n", what, t - mark);
+        mark = t;
     }
-    *out_count = n;
+};
+
+int upload(void* dst, const void* src, size_t bytes) {
+    if (bytes) HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
     return CALIB_OK;
 }
 
-int calib_create(int model, int dtype, int device_id, calib_handle_t* out_handle) {
-    if (!out_handle) return fail(CALIB_E_INVALID, "out_handle is null");
-    *out_handle = nullptr;
-    if (model != CALIB_MODEL_RADTAN && model != CALIB_MODEL_FISHEYE)
-        return fail(CALIB_E_INVALID, "unknown distortion model");
-    if (dtype != CALIB_DTYPE_F64 && dtype != CALIB_DTYPE_F32)
-        return fail(CALIB_E_INVALID, "unknown dtype");
-    int n = 0;
-    HIP_TRY(hipGetDeviceCount(&n));
-    if (device_id < 0 || device_id >= n)
-        return fail(CALIB_E_HIP, "no such HIP device (this library has no CPU fallback)");
-    HIP_TRY(hipSetDevice(device_id));
-    calib_handle_s* h = new (std::nothrow) calib_handle_s();
-    if (!h) return fail(CALIB_E_INVALID, "out of host memory");
-    h->model = model;
-    h->dtype = dtype;
-    h->device = device_id;
-    h->L = model == CALIB_MODEL_RADTAN ? 10 : 9;
-    h->C = h->L + 6;
-    hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-        delete h;
-        return fail(CALIB_E_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
+// Everything O(points) -- the AoS -> SoA split, the storage-type conversion, the point -> view index -- happens on
+// the device, from the caller's arrays uploaded as they are.
+int pack_points(calib_handle_s* h, const ShardLayout& lay, const HostRows& sensor_uv, const HostRows& model_xyz, Laps& lap) {
+    const int64_t MN = h->MN;
+    DevBuf<double> xyz_stage, uv_stage;
+    DevBuf<int64_t> dvoffs;
+    HIP_TRY(xyz_stage.alloc((size_t)MN * 3));
+    HIP_TRY(dvoffs.alloc(lay.voffs.size()));
+    int rc = upload(dvoffs.p, lay.voffs.data(), lay.voffs.size() * 8);
+    if (rc) return rc;
+    lap("small uploads + stage alloc");
+    rc = upload_staged(h, xyz_stage.p, model_xyz, (size_t)MN * 24);
+    if (rc) return rc;
+    lap("staged upload xyz");
+    int uv_mode = 2;
+    const double* uv_in = nullptr;
+    if (sensor_uv.present() && h->dtype == CALIB_DTYPE_F64) {   // already in the device layout
+        rc = upload_staged(h, h->uv.p, sensor_uv, (size_t)MN * 16);
+        if (rc) return rc;
+        uv_mode = 0;
+    } else if (sensor_uv.present()) {
+        HIP_TRY(uv_stage.alloc((size_t)MN * 2));
+        rc = upload_staged(h, uv_stage.p, sensor_uv, (size_t)MN * 16);
+        if (rc) return rc;
+        uv_in = uv_stage.p;
+        uv_mode = 1;
     }
-    h->stream = h->own_stream;
-    {
-        uint32_t tab[kEmitTabSize];
-        buildEmitTable(h->C, tab);
-        e = h->emit_tab.alloc(kEmitTabSize);
-        if (e == hipSuccess) e = hipMemcpy(h->emit_tab.p, tab, sizeof(tab), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            h->emit_tab.release();
-            (void)hipStreamDestroy(h->own_stream);
-            delete h;
-            return fail(CALIB_E_HIP, std::string("emit table: ") + hipGetErrorString(e));
-        }
-    }
-    {
-        int32_t ops[64 * kStreamOps];
-        const bool built = buildStreamOps(h->C, ops);
-        e = built ? h->stream_ops.alloc(64 * kStreamOps) : hipErrorUnknown;
-        if (e == hipSuccess) e = hipMemcpy(h->stream_ops.p, ops, sizeof(ops), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            h->emit_tab.release();
-            h->stream_ops.release();
-            (void)hipStreamDestroy(h->own_stream);
-            delete h;
-            return fail(CALIB_E_HIP, std::string("stream record table: ") + (built ? hipGetErrorString(e) : "inconsistent"));
-        }
-    }
-    h->knobs = readKnobs();
-    h->lm_mode = h->knobs.lm_mode;
-    {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_id) == hipSuccess && cus > 0)
-            h->num_cus = cus;
-    }
-    *out_handle = h;
+    lap("staged upload uv");
+    const unsigned blocks = (unsigned)((MN + 255) / 256);
+    rc = dispatch(h, [&](auto form) -> int {
+        using T = typename decltype(form)::T;
+        using T2 = typename decltype(form)::T2;
+        hipLaunchKernelGGL((pack_points_kernel<T>), dim3(blocks), dim3(256), 0, h->stream, xyz_stage.p, uv_in, uv_mode,
+                           dvoffs.p, h->nv, MN, h->XY_as<T2>(), h->Z_as<T>(), h->uv_as<T2>(), h->pt_view.p);
+        LAUNCHED(h, "pack_points_kernel");
+        return CALIB_OK;
+    });
+    if (rc) return rc;
+    SYNC_H(h);                   // the staging buffers go out of scope
+    lap("pack kernel");
     return CALIB_OK;
 }
 
-namespace {
+int set_problem_impl(calib_handle_t h, int64_t num_views, const int64_t* view_offsets, const HostRows& sensor_uv,
+                     const HostRows& model_xyz) {
+    CHECK_H(h);
+    if (num_views < 0 || !view_offsets) return fail(CALIB_E_INVALID, "bad view_offsets");
+    if (view_offsets[0] != 0) return fail(CALIB_E_INVALID, "view_offsets[0] must be 0");
+    for (int64_t i = 0; i < num_views; ++i)
+        if (view_offsets[i + 1] < view_offsets[i])
+            return fail(CALIB_E_INVALID, "view_offsets must be non-decreasing");
+    const int64_t MN = view_offsets[num_views];
+    if (MN > 0 && !model_xyz.present()) return fail(CALIB_E_INVALID, "model_xyz is null");
+    if (num_views > 0x7fffffffLL / 8 || MN > (int64_t)1 << 40)
+        return fail(CALIB_E_INVALID, "problem too large for one shard");
+    SYNC_H(h);
+    h->has_problem = false;
+    h->lm_active = false;
+    h->cov_pending = false;
+    h->ext_offsets.assign(view_offsets, view_offsets + num_views + 1);
+    h->ext_offsets_on_device = false;
+    h->M = num_views;
+    h->MN = MN;
+
+    Laps lap{h->knobs.timing};
+    ShardLayout lay = makeShardLayout(num_views, view_offsets, h->knobs.chunk_points);
+    h->nv = lay.nv;
+    h->n_items = lay.n_items;
+    h->n_tiles = lay.n_tiles;
+    h->max_views_per_tile = lay.max_views_per_tile;
+    h->uniform_n = lay.uniform_n;
+    h->chunks = std::move(lay.chunks);
+    h->max_chunk_points = lay.max_chunk_points;
+    lap("host view/item lists");
+
+    const size_t ts = tsize(h);
+    HIP_TRY(h->uv.alloc((size_t)MN * 2 * ts));
+    HIP_TRY(h->XY.alloc((size_t)MN * 2 * ts));
+    HIP_TRY(h->Z.alloc((size_t)MN * ts));
+    HIP_TRY(h->pt_view.alloc((size_t)MN));
+    HIP_TRY(h->view_ext.alloc((size_t)h->nv));
+    HIP_TRY(h->item_n.alloc((size_t)h->n_items));
+    HIP_TRY(h->item_view.alloc((size_t)h->n_items));
+    HIP_TRY(h->item_pt0.alloc((size_t)h->n_items));
+    HIP_TRY(h->view_item0.alloc((size_t)h->nv + 1));
+    HIP_TRY(h->VC.alloc((size_t)std::max(h->nv, 1) * kViewStride * ts));
+    HIP_TRY(h->r.alloc((size_t)MN * 2 * ts));
+    HIP_TRY(h->sse_part.alloc((size_t)std::max<int64_t>(h->n_tiles, 1)));
+    HIP_TRY(h->st_eval.alloc(1));
+    HIP_TRY(hipMemsetAsync(h->st_eval.p, 0, sizeof(LMState), h->stream));
+    HIP_TRY(h->Peval.alloc((size_t)numParams(h)));
+    lap("device allocations");
+
+    h->plan = plan_of(h);
+    const struct { void* dst; const void* src; size_t bytes; } tables[] = {
+        {h->view_ext.p, lay.view_ext.data(), lay.view_ext.size() * 4},
+        {h->item_n.p, lay.item_n.data(), lay.item_n.size() * 4},
+        {h->item_view.p, lay.item_view.data(), lay.item_view.size() * 4},
+        {h->item_pt0.p, lay.item_pt0.data(), lay.item_pt0.size() * 8},
+        {h->view_item0.p, lay.view_item0.data(), lay.view_item0.size() * 4},
+    };
+    for (const auto& t : tables) {
+        const int rc = upload(t.dst, t.src, t.bytes);
+        if (rc) return rc;
+    }
+    if (MN > 0) {
+        const int rc = pack_points(h, lay, sensor_uv, model_xyz, lap);
+        if (rc) return rc;
+    }
+    h->has_problem = true;
+    return CALIB_OK;
+}
+
+// ---- peer exchange, LM run ---------------------------------------------------------------------
 // Slot memory exported by handles of THIS process (one process driving several handles / GPUs): HIP IPC
 // cannot open a handle in the process that made it, so calib_peer_connect looks here first.
 struct LocalSlots { hipIpcMemHandle_t ipc; void* mem; int device; };
@@ -626,8 +676,232 @@ void peer_release(calib_handle_s* h) {
     h->peer_connected = false;
     h->peer_world = 0;
 }
+
+// after a synchronisation: did a peer exchange of this handle give up waiting for a rank?
+int peer_fault_check(calib_handle_s* h) {
+    if (!h->peer_connected) return CALIB_OK;
+    int fault = 0;
+    HIP_TRY(hipMemcpy(&fault, h->peer_flags.p, sizeof(int), hipMemcpyDeviceToHost));
+    if (fault)
+        return fail(CALIB_E_HIP, "peer exchange: a rank's contribution did not arrive before the deadline "
+                                 "(the ranks no longer run in lockstep, or a peer died)");
+    return CALIB_OK;
+}
+
+// the end of a run: wait for it, read the LM state, then the peer-fault check and the singular check
+int lm_finish(calib_handle_s* h, LMState* s) {
+    SYNC_H(h);
+    HIP_TRY(hipMemcpy(s, st_cur(h), sizeof(*s), hipMemcpyDeviceToHost));
+    h->lm_active = false;
+    const int prc = peer_fault_check(h);
+    if (prc) return prc;
+    if (s->error == CALIB_E_SINGULAR)
+        return fail(CALIB_E_SINGULAR, "Singular matrix: damped normal equations are not invertible");
+    return CALIB_OK;
+}
+
+int lm_run(calib_handle_t h, int rounds, int check_every, bool sharded) {
+    CHECK_H(h);
+    if (!h->lm_active) return fail(CALIB_E_STATE, "calib_lm_begin has not been called");
+    const bool peers = sharded && h->peer_connected;      // the reduce kernel sums over the ranks itself
+    for (int i = 0; i < rounds; ++i) {
+        h->exchange_round = peers;
+        int rc = calib_lm_local(h);
+        h->exchange_round = false;
+        if (rc) return rc;
+        if (sharded && !peers) {
+            rc = calib_lm_allreduce(h);
+            if (rc) return rc;
+        }
+        rc = calib_lm_update(h);
+        if (rc) return rc;
+        if (peers && h->host_done && *static_cast<volatile int*>(h->host_done) == 2)
+            return fail(CALIB_E_HIP, "peer exchange: a rank's contribution did not arrive before the deadline "
+                                     "(the ranks no longer run in lockstep, or a peer died); no further rounds are enqueued");
+        if (check_every > 0 && !sharded && h->host_done) {
+            // single shard: the device says so in host-visible memory when the loop is over -- no synchronisation, the
+            // host simply stops enqueueing (rounds already in the queue exit at once)
+            if (*static_cast<volatile int*>(h->host_done)) break;
+        } else if (check_every > 0 && (i + 1) % check_every == 0 && i + 1 < rounds) {
+            // sharded: every rank must enqueue the same rounds, so all of them look at the (replicated) flag at the
+            // same round numbers
+            int done = 0;
+            rc = calib_lm_done(h, &done);
+            if (rc) return rc;
+            if (done) break;
+        }
+    }
+    return CALIB_OK;
+}
+
+// ---- entry points without a handle: the closed-form stages -------------------------------------
+int check_views(int64_t num_views, const int64_t* view_offsets, const double* sensor_uv, const double* model_xyz) {
+    if (num_views < 0 || !view_offsets) return fail(CALIB_E_INVALID, "null argument");
+    if (num_views == 0) return CALIB_OK;
+    const int64_t MN = view_offsets[num_views];
+    if (view_offsets[0] != 0 || MN < 0 || (MN > 0 && (!sensor_uv || !model_xyz)))
+        return fail(CALIB_E_INVALID, "bad view_offsets / point arrays");
+    for (int64_t i = 0; i < num_views; ++i)
+        if (view_offsets[i + 1] < view_offsets[i]) return fail(CALIB_E_INVALID, "view_offsets must be non-decreasing");
+    return CALIB_OK;
+}
+
+int use_device(int device_id) {
+    int ndev = 0;
+    HIP_TRY(hipGetDeviceCount(&ndev));
+    if (device_id < 0 || device_id >= ndev) return fail(CALIB_E_HIP, "no such HIP device (no CPU fallback)");
+    HIP_TRY(hipSetDevice(device_id));
+    return CALIB_OK;
+}
+
+// DLT and / or LM polish of every view's homography
+int homography_pipeline(int64_t num_views, const int64_t* view_offsets, const double* sensor_uv,
+                        const double* model_xyz, double* H, bool dlt, int refine_iters, int device_id) {
+    if (!H) return fail(CALIB_E_INVALID, "null argument");
+    int rc = check_views(num_views, view_offsets, sensor_uv, model_xyz);
+    if (rc || num_views == 0) return rc;
+    rc = use_device(device_id);
+    if (rc) return rc;
+    const int64_t MN = view_offsets[num_views];
+    std::vector<double> xy((size_t)MN * 2);
+    for (int64_t p = 0; p < MN; ++p) { xy[2 * p] = model_xyz[3 * p]; xy[2 * p + 1] = model_xyz[3 * p + 1]; }
+    DevBuf<int64_t> doffs;
+    DevBuf<double2> duv, dxy;
+    DevBuf<double> dH;
+    HIP_TRY(doffs.alloc((size_t)num_views + 1));
+    HIP_TRY(duv.alloc((size_t)std::max<int64_t>(MN, 1)));
+    HIP_TRY(dxy.alloc((size_t)std::max<int64_t>(MN, 1)));
+    HIP_TRY(dH.alloc((size_t)num_views * 9));
+    HIP_TRY(hipMemcpy(doffs.p, view_offsets, ((size_t)num_views + 1) * 8, hipMemcpyHostToDevice));
+    if (MN) HIP_TRY(hipMemcpy(duv.p, sensor_uv, (size_t)MN * 16, hipMemcpyHostToDevice));
+    if (MN) HIP_TRY(hipMemcpy(dxy.p, xy.data(), (size_t)MN * 16, hipMemcpyHostToDevice));
+    if (!dlt) HIP_TRY(hipMemcpy(dH.p, H, (size_t)num_views * 72, hipMemcpyHostToDevice));
+    const unsigned blocks = (unsigned)((num_views + 15) / 16);
+    if (dlt) {
+        hipLaunchKernelGGL(dlt_kernel, dim3(blocks), dim3(256), 0, 0, doffs.p, (const double2*)duv.p, (const double2*)dxy.p,
+                           num_views, dH.p);
+        LAUNCHED(kNoHandle, "dlt_kernel");
+    }
+    if (refine_iters > 0) {
+        hipLaunchKernelGGL(homography_lm_kernel, dim3(blocks), dim3(256), 0, 0, doffs.p, (const double2*)duv.p,
+                           (const double2*)dxy.p, num_views, refine_iters, dH.p);
+        LAUNCHED(kNoHandle, "homography_lm_kernel");
+    }
+    HIP_TRY(hipMemcpy(H, dH.p, (size_t)num_views * 72, hipMemcpyDeviceToHost));
+    return CALIB_OK;
+}
+
+// ---- uncertainty (calib_cov_finish) ------------------------------------------------------------
+// sigma2 (S_free)^-1 of the reduced system S = Bsum - Ssub, zero-padded to L x L for the fixed parameters: Cholesky of
+// the free sub-matrix (lower triangle), its inverse by substitution, mirrored so that the result is exactly symmetric.
+// Pure host arithmetic on the all-reduced buffer: every rank of a sharded run gets the same bits.
+bool shared_covariance(const double* red, int L, uint32_t fixed_mask, double sigma2, double* Css /* L*L */) {
+    int idx[kMaxL], n = 0;
+    for (int i = 0; i < L; ++i) if (!((fixed_mask >> i) & 1)) idx[n++] = i;
+    double S[kMaxL][kMaxL], X[kMaxL][kMaxL];
+    for (int a = 0; a < n; ++a)
+        for (int b = 0; b <= a; ++b) S[a][b] = red[idx[a] * L + idx[b]] - red[L * L + idx[a] * L + idx[b]];
+    for (int j = 0; j < n; ++j) {                        // S = Lc Lc^T, in place
+        double d = S[j][j];
+        for (int q = 0; q < j; ++q) d -= S[j][q] * S[j][q];
+        if (!(d > 0.0)) return false;
+        S[j][j] = std::sqrt(d);
+        for (int i = j + 1; i < n; ++i) {
+            double t = S[i][j];
+            for (int q = 0; q < j; ++q) t -= S[i][q] * S[j][q];
+            S[i][j] = t / S[j][j];
+        }
+    }
+    for (int c = 0; c < n; ++c) {                        // column c of the inverse
+        double z[kMaxL];
+        for (int i = 0; i < n; ++i) {
+            double t = i == c ? 1.0 : 0.0;
+            for (int q = 0; q < i; ++q) t -= S[i][q] * z[q];
+            z[i] = t / S[i][i];
+        }
+        for (int i = n - 1; i >= 0; --i) {
+            double t = z[i];
+            for (int q = i + 1; q < n; ++q) t -= S[q][i] * X[q][c];
+            X[i][c] = t / S[i][i];
+        }
+    }
+    std::fill(Css, Css + L * L, 0.0);
+    for (int a = 0; a < n; ++a)
+        for (int b = 0; b <= a; ++b) {
+            const double v = sigma2 * X[a][b];
+            Css[idx[a] * L + idx[b]] = v;
+            Css[idx[b] * L + idx[a]] = v;
+        }
+    return true;
+}
 }  // namespace
 
+// ============================================================================ C-ABI
+extern "C" {
+
+int calib_version(void) { return 420; }   // 4.2: calib_view_errors, calib_cov_local / calib_cov_finish / calib_covariance
+
+const char* calib_last_error(void) { return g_err.c_str(); }
+
+int calib_device_count(int* out_count) {
+    if (!out_count) return fail(CALIB_E_INVALID, "out_count is null");
+    int n = 0;
+    hipError_t e = hipGetDeviceCount(&n);
+    if (e != hipSuccess) {
+        *out_count = 0;
+        return fail(CALIB_E_HIP, std::string("hipGetDeviceCount: ") + hipGetErrorString(e));
+    }
+    *out_count = n;
+    return CALIB_OK;
+}
+
+
+int calib_create(int model, int dtype, int device_id, calib_handle_t* out_handle) {
+    if (!out_handle) return fail(CALIB_E_INVALID, "out_handle is null");
+    *out_handle = nullptr;
+    if (!known_model(model)) return fail(CALIB_E_INVALID, "unknown distortion model");
+    if (dtype != CALIB_DTYPE_F64 && dtype != CALIB_DTYPE_F32)
+        return fail(CALIB_E_INVALID, "unknown dtype");
+    int n = 0;
+    HIP_TRY(hipGetDeviceCount(&n));
+    if (device_id < 0 || device_id >= n)
+        return fail(CALIB_E_HIP, "no such HIP device (this library has no CPU fallback)");
+    HIP_TRY(hipSetDevice(device_id));
+    // the half-built handle is owned here: every early return below destroys what it holds
+    std::unique_ptr<calib_handle_s, int (*)(calib_handle_t)> h(new (std::nothrow) calib_handle_s(), calib_destroy);
+    if (!h) return fail(CALIB_E_INVALID, "out of host memory");
+    h->model = model;
+    h->dtype = dtype;
+    h->device = device_id;
+    h->L = 5 + num_distortion(model);
+    h->C = h->L + 6;
+    HIP_TRY(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
+    h->stream = h->own_stream;
+    {
+        uint32_t tab[kEmitTabSize];
+        buildEmitTable(h->C, tab);
+        HIP_TRY(h->emit_tab.alloc(kEmitTabSize));
+        HIP_TRY(hipMemcpy(h->emit_tab.p, tab, sizeof(tab), hipMemcpyHostToDevice));
+    }
+    {
+        int32_t ops[64 * kStreamOps];
+        if (!buildStreamOps(h->C, ops)) return fail(CALIB_E_HIP, "stream record table: inconsistent");
+        HIP_TRY(h->stream_ops.alloc(64 * kStreamOps));
+        HIP_TRY(hipMemcpy(h->stream_ops.p, ops, sizeof(ops), hipMemcpyHostToDevice));
+    }
+    h->knobs = readKnobs();
+    h->lm_mode = h->knobs.lm_mode;
+    {
+        int cus = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_id) == hipSuccess && cus > 0)
+            h->num_cus = cus;
+    }
+    *out_handle = h.release();
+    return CALIB_OK;
+}
+
+// What the members' destructors cannot do, in this order: the stream is drained before anything is freed; the
+// device buffers (DevBuf) go with `delete`.
 int calib_destroy(calib_handle_t h) {
     if (!h) return CALIB_OK;
     (void)hipSetDevice(h->device);
@@ -643,13 +917,6 @@ int calib_destroy(calib_handle_t h) {
         }
     if (h->stage_pinned) (void)hipHostFree(h->stage_pinned);
     if (h->host_done) (void)hipHostFree(h->host_done);
-    h->uv.release(); h->XY.release(); h->Z.release(); h->VC.release(); h->J.release();
-    h->r.release(); h->y.release(); h->pt_view.release(); h->view_ext.release();
-    h->item_n.release(); h->view_item0.release(); h->item_view.release(); h->item_pt0.release(); h->sse_part.release();
-    h->emit_tab.release(); h->stream_ops.release();
-    h->G[0].release(); h->G[1].release(); h->bpart.release(); h->part.release(); h->red_own.release();
-    h->P[0].release(); h->P[1].release(); h->Peval.release(); h->trace.release();
-    h->st.release(); h->st_eval.release(); h->rccl_test.release();
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
     delete h;
     return CALIB_OK;
@@ -710,13 +977,6 @@ int calib_num_params(calib_handle_t h, int64_t* out_K) {
     return CALIB_OK;
 }
 
-}  // extern "C"
-namespace {
-int set_problem_impl(calib_handle_t h, int64_t num_views, const int64_t* view_offsets, const HostRows& sensor_uv,
-                     const HostRows& model_xyz);
-}
-extern "C" {
-
 int calib_set_problem(calib_handle_t h, int64_t num_views, const int64_t* view_offsets,
                       const double* sensor_uv, const double* model_xyz) {
     HostRows s, m;
@@ -738,180 +998,6 @@ int calib_set_problem_views(calib_handle_t h, int64_t num_views, const int64_t* 
     return set_problem_impl(h, num_views, view_offsets, s, m);
 }
 
-}  // extern "C"
-namespace {
-int set_problem_impl(calib_handle_t h, int64_t num_views, const int64_t* view_offsets, const HostRows& sensor_uv,
-                     const HostRows& model_xyz) {
-    CHECK_H(h);
-    if (num_views < 0 || !view_offsets) return fail(CALIB_E_INVALID, "bad view_offsets");
-    if (view_offsets[0] != 0) return fail(CALIB_E_INVALID, "view_offsets[0] must be 0");
-    for (int64_t i = 0; i < num_views; ++i)
-        if (view_offsets[i + 1] < view_offsets[i])
-            return fail(CALIB_E_INVALID, "view_offsets must be non-decreasing");
-    const int64_t MN = view_offsets[num_views];
-    if (MN > 0 && !model_xyz.present()) return fail(CALIB_E_INVALID, "model_xyz is null");
-    if (num_views > 0x7fffffffLL / 8 || MN > (int64_t)1 << 40)
-        return fail(CALIB_E_INVALID, "problem too large for one shard");
-    SYNC_H(h);
-    h->has_problem = false;
-    h->lm_active = false;
-    h->cov_pending = false;
-    h->ext_offsets.assign(view_offsets, view_offsets + num_views + 1);
-    h->ext_offsets_on_device = false;
-    h->M = num_views;
-    h->MN = MN;
-
-    const bool timing = h->knobs.timing;
-    auto tnow = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double tmark = tnow();
-    auto lap = [&](const char* what) { if (timing) { const double t = tnow(); std::fprintf(stderr, "  set_problem %-28s %.3f ms\n", what, t - tmark); tmark = t; } };
-    // host side, O(views): compact (non-empty) view list, their point offsets, gram / fused work items.
-    // Everything O(points) -- the AoS -> SoA split, the storage-type conversion, the point -> view index --
-    // happens on the device from the caller's arrays uploaded as they are (pack_points_kernel).
-    std::vector<int> view_ext, item_n, view_item0, item_view;
-    std::vector<int64_t> item_pt0, voffs;
-    view_item0.push_back(0);
-    for (int64_t i = 0; i < num_views; ++i) {
-        const int64_t a = view_offsets[i], b = view_offsets[i + 1];
-        if (b == a) continue;
-        const int cv = (int)view_ext.size();
-        view_ext.push_back((int)i);
-        voffs.push_back(a);
-        for (int64_t p = a; p < b; p += kGramChunk) {
-            item_pt0.push_back(p);
-            item_n.push_back((int)std::min<int64_t>(kGramChunk, b - p));
-            item_view.push_back(cv);
-        }
-        view_item0.push_back((int)item_pt0.size());
-    }
-    voffs.push_back(MN);
-    h->nv = (int)view_ext.size();
-    h->n_items = (int)item_pt0.size();
-    // compact view of point p (points of the non-empty views are contiguous)
-    auto viewOf = [&](int64_t p) { return (int)(std::upper_bound(voffs.begin(), voffs.end(), p) - voffs.begin()) - 1; };
-    h->n_tiles = (MN + kTile - 1) / kTile;
-    int mv = 1;
-    {   // views spanned by a 256-point tile (what the jacobian kernel stages in LDS): one sweep over the offsets
-        int va = 0, vb = 0;
-        for (int64_t t = 0; t < h->n_tiles; ++t) {
-            const int64_t a = t * kTile, b = std::min<int64_t>(MN, a + kTile) - 1;
-            while (voffs[(size_t)va + 1] <= a) ++va;
-            if (vb < va) vb = va;
-            while (voffs[(size_t)vb + 1] <= b) ++vb;
-            mv = std::max(mv, vb - va + 1);
-        }
-    }
-    {   // chunks of whole views, ~chunk_points each; tiles of a chunk start at the chunk's first point
-        // Measured on MI355X (c3, 2 M points): chunks small enough for the 256 MiB Infinity Cache
-        // do NOT make the J round trip cheaper (0.33 ms/iter at one chunk, 0.45 at 262 k points,
-        // 1.1 at 65 k), so the chunk only bounds the J buffer: 64 M points = 17 GB at C = 16, fp64.
-        const int64_t target = h->knobs.chunk_points;
-        h->chunks.clear();
-        h->max_chunk_points = 0;
-        int v = 0;
-        while (v < h->nv) {
-            calib_handle_s::Chunk c;
-            c.p0 = item_pt0[(size_t)view_item0[(size_t)v]];
-            c.item0 = view_item0[(size_t)v];
-            int64_t p1 = c.p0;
-            while (v < h->nv && (p1 - c.p0 < target)) {
-                const int last = view_item0[(size_t)v + 1] - 1;
-                p1 = item_pt0[(size_t)last] + item_n[(size_t)last];
-                ++v;
-            }
-            c.p1 = p1;
-            c.item1 = view_item0[(size_t)v];
-            const bool whole = h->chunks.empty() && v >= h->nv;       // one chunk = the tiles counted above
-            h->chunks.push_back(c);
-            h->max_chunk_points = std::max(h->max_chunk_points, c.p1 - c.p0);
-            if (!whole)
-                for (int64_t a = c.p0; a < c.p1; a += kTile) {
-                    const int64_t b = std::min<int64_t>(c.p1, a + kTile) - 1;
-                    mv = std::max(mv, viewOf(b) - viewOf(a) + 1);
-                }
-        }
-    }
-    h->max_views_per_tile = mv;
-
-    lap("host view/item lists");
-    const size_t ts = tsize(h);
-    HIP_TRY(h->uv.alloc((size_t)MN * 2 * ts));
-    HIP_TRY(h->XY.alloc((size_t)MN * 2 * ts));
-    HIP_TRY(h->Z.alloc((size_t)MN * ts));
-    HIP_TRY(h->pt_view.alloc((size_t)MN));
-    HIP_TRY(h->view_ext.alloc((size_t)h->nv));
-    HIP_TRY(h->item_n.alloc((size_t)h->n_items));
-    HIP_TRY(h->item_view.alloc((size_t)h->n_items));
-    HIP_TRY(h->item_pt0.alloc((size_t)h->n_items));
-    HIP_TRY(h->view_item0.alloc((size_t)h->nv + 1));
-    HIP_TRY(h->VC.alloc((size_t)std::max(h->nv, 1) * kViewStride * ts));
-    HIP_TRY(h->r.alloc((size_t)MN * 2 * ts));
-    HIP_TRY(h->sse_part.alloc((size_t)std::max<int64_t>(h->n_tiles, 1)));
-    HIP_TRY(h->st_eval.alloc(1));
-    HIP_TRY(hipMemsetAsync(h->st_eval.p, 0, sizeof(LMState), h->stream));
-    HIP_TRY(h->Peval.alloc((size_t)numParams(h)));
-
-    lap("device allocations");
-    auto upload = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
-        if (bytes == 0) return hipSuccess;
-        return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice);
-    };
-    HIP_TRY(upload(h->view_ext.p, view_ext.data(), view_ext.size() * 4));
-    {
-        // uniform shards (every view fully detected: the usual case) need no item tables in the fused kernel
-        int un = item_n.empty() ? 0 : item_n[0];
-        for (size_t i = 0; i < item_n.size() && un > 0; ++i)
-            if (item_n[i] != un || item_pt0[i] != (int64_t)i * un || item_view[i] != (int)i) un = 0;
-        h->uniform_n = un;
-    }
-    h->plan = plan_of(h);
-    HIP_TRY(upload(h->item_n.p, item_n.data(), item_n.size() * 4));
-    HIP_TRY(upload(h->item_view.p, item_view.data(), item_view.size() * 4));
-    HIP_TRY(upload(h->item_pt0.p, item_pt0.data(), item_pt0.size() * 8));
-    HIP_TRY(upload(h->view_item0.p, view_item0.data(), view_item0.size() * 4));
-    if (MN > 0) {
-        DevBuf<double> xyz_stage, uv_stage;
-        DevBuf<int64_t> dvoffs;
-        HIP_TRY(xyz_stage.alloc((size_t)MN * 3));
-        HIP_TRY(dvoffs.alloc(voffs.size()));
-        HIP_TRY(upload(dvoffs.p, voffs.data(), voffs.size() * 8));
-        lap("small uploads + stage alloc");
-        int rc = upload_staged(h, xyz_stage.p, model_xyz, (size_t)MN * 24);
-        if (rc) return rc;
-        lap("staged upload xyz");
-        int uv_mode = 2;
-        const double* uv_in = nullptr;
-        if (sensor_uv.present() && h->dtype == CALIB_DTYPE_F64) {   // already in the device layout
-            rc = upload_staged(h, h->uv.p, sensor_uv, (size_t)MN * 16);
-            if (rc) return rc;
-            uv_mode = 0;
-        } else if (sensor_uv.present()) {
-            HIP_TRY(uv_stage.alloc((size_t)MN * 2));
-            rc = upload_staged(h, uv_stage.p, sensor_uv, (size_t)MN * 16);
-            if (rc) return rc;
-            uv_in = uv_stage.p;
-            uv_mode = 1;
-        }
-        lap("staged upload uv");
-        const unsigned blocks = (unsigned)((MN + 255) / 256);
-        if (h->dtype == CALIB_DTYPE_F64)
-            hipLaunchKernelGGL((pack_points_kernel<double>), dim3(blocks), dim3(256), 0, h->stream, xyz_stage.p, uv_in,
-                               uv_mode, dvoffs.p, h->nv, MN, reinterpret_cast<double2*>(h->XY.p),
-                               reinterpret_cast<double*>(h->Z.p), reinterpret_cast<double2*>(h->uv.p), h->pt_view.p);
-        else
-            hipLaunchKernelGGL((pack_points_kernel<float>), dim3(blocks), dim3(256), 0, h->stream, xyz_stage.p, uv_in,
-                               uv_mode, dvoffs.p, h->nv, MN, reinterpret_cast<float2*>(h->XY.p),
-                               reinterpret_cast<float*>(h->Z.p), reinterpret_cast<float2*>(h->uv.p), h->pt_view.p);
-        LAUNCHED(h, "pack_points_kernel");
-        SYNC_H(h);                   // the staging buffers go out of scope
-        lap("pack kernel");
-    }
-    h->has_problem = true;
-    return CALIB_OK;
-}
-}  // namespace
-extern "C" {
-
 int calib_eval(calib_handle_t h, const double* P, double* out_y, double* out_r, double* out_Jc,
                double* out_sse) {
     CHECK_H(h);
@@ -925,7 +1011,7 @@ int calib_eval(calib_handle_t h, const double* P, double* out_y, double* out_r, 
     if (out_y) HIP_TRY(h->y.alloc((size_t)MN * 2 * ts));
     HIP_TRY(h->red_own.alloc((size_t)reduceSize(h->L)));
     HIP_TRY(hipMemcpyAsync(h->Peval.p, P, (size_t)numParams(h) * 8, hipMemcpyHostToDevice, h->stream));
-    rc = launch_view_setup_any(h, h->Peval.p, nullptr, h->st_eval.p, 0);
+    rc = launch_view_setup(h, h->Peval.p, nullptr, h->st_eval.p, 0);
     if (rc) return rc;
     rc = launch_jacobian(h, h->Peval.p, nullptr, h->st_eval.p, 0, out_Jc != nullptr, out_r != nullptr,
                          out_y != nullptr, true, 0, MN);
@@ -1055,7 +1141,7 @@ int calib_lm_local(calib_handle_t h) {
     LMState* st = st_cur(h);
     int rc = CALIB_OK;
     if (h->rounds_enqueued == 0) {      // later rounds: the update kernel already wrote the candidate's constants
-        rc = launch_view_setup_any(h, h->P[0].p, h->P[1].p, st, 1);
+        rc = launch_view_setup(h, h->P[0].p, h->P[1].p, st, 1);
         if (rc) return rc;
     }
     if (h->lm_mode == CALIB_LM_FUSED) {
@@ -1081,19 +1167,6 @@ int calib_lm_update(calib_handle_t h) {
     return rc;
 }
 
-namespace {
-// after a synchronisation: did a peer exchange of this handle give up waiting for a rank?
-int peer_fault_check(calib_handle_s* h) {
-    if (!h->peer_connected) return CALIB_OK;
-    int fault = 0;
-    HIP_TRY(hipMemcpy(&fault, h->peer_flags.p, sizeof(int), hipMemcpyDeviceToHost));
-    if (fault)
-        return fail(CALIB_E_HIP, "peer exchange: a rank's contribution did not arrive before the deadline "
-                                 "(the ranks no longer run in lockstep, or a peer died)");
-    return CALIB_OK;
-}
-}  // namespace
-
 int calib_lm_done(calib_handle_t h, int* out_done) {
     CHECK_H(h);
     if (!h->lm_active || !out_done) return fail(CALIB_E_STATE, "no LM run active");
@@ -1117,10 +1190,6 @@ int calib_lm_peek_trace(calib_handle_t h, int iter, double* out_row, int* out_it
     return CALIB_OK;
 }
 
-namespace {
-int lm_run(calib_handle_t h, int rounds, int check_every, bool sharded);
-}
-
 int calib_lm_run(calib_handle_t h, int rounds, int check_every) { return lm_run(h, rounds, check_every, false); }
 
 int calib_lm_run_sharded(calib_handle_t h, int rounds, int check_every) {
@@ -1128,42 +1197,6 @@ int calib_lm_run_sharded(calib_handle_t h, int rounds, int check_every) {
         return fail(CALIB_E_STATE, "neither calib_peer_connect nor calib_rccl_init has been called");
     return lm_run(h, rounds, check_every, true);
 }
-
-namespace {
-int lm_run(calib_handle_t h, int rounds, int check_every, bool sharded) {
-    CHECK_H(h);
-    if (!h->lm_active) return fail(CALIB_E_STATE, "calib_lm_begin has not been called");
-    const bool peers = sharded && h->peer_connected;      // the reduce kernel sums over the ranks itself
-    for (int i = 0; i < rounds; ++i) {
-        h->exchange_round = peers;
-        int rc = calib_lm_local(h);
-        h->exchange_round = false;
-        if (rc) return rc;
-        if (sharded && !peers) {
-            rc = calib_lm_allreduce(h);
-            if (rc) return rc;
-        }
-        rc = calib_lm_update(h);
-        if (rc) return rc;
-        if (peers && h->host_done && *static_cast<volatile int*>(h->host_done) == 2)
-            return fail(CALIB_E_HIP, "peer exchange: a rank's contribution did not arrive before the deadline "
-                                     "(the ranks no longer run in lockstep, or a peer died); no further rounds are enqueued");
-        if (check_every > 0 && !sharded && h->host_done) {
-            // single shard: the device says so in host-visible memory when the loop is over -- no synchronisation, the
-            // host simply stops enqueueing (rounds already in the queue exit at once)
-            if (*static_cast<volatile int*>(h->host_done)) break;
-        } else if (check_every > 0 && (i + 1) % check_every == 0 && i + 1 < rounds) {
-            // sharded: every rank must enqueue the same rounds, so all of them look at the (replicated) flag at the
-            // same round numbers
-            int done = 0;
-            rc = calib_lm_done(h, &done);
-            if (rc) return rc;
-            if (done) break;
-        }
-    }
-    return CALIB_OK;
-}
-}  // namespace
 
 int calib_rccl_load(const char* librccl_path) {
     std::lock_guard<std::mutex> lock(g_rccl_mutex);
@@ -1261,9 +1294,7 @@ int calib_rccl_selftest(calib_handle_t h, double timeout_s) {
     int rc = g_rccl.allReduce(h->rccl_test.p, h->rccl_test.p, 4, kNcclDouble, kNcclSum, h->comm, h->stream);
     if (rc) { giveUp(); return rccl_fail("ncclAllReduce (self-test)", rc); }
     const auto deadline = std::chrono::steady_clock::now() + std::chrono::duration<double>(timeout_s > 0 ? timeout_s : 30.0);
-    for (;;) {
-        const hipError_t e = hipStreamQuery(h->stream);
-        if (e == hipSuccess) break;
+    for (hipError_t e; (e = hipStreamQuery(h->stream)) != hipSuccess;) {
         if (e != hipErrorNotReady) { giveUp(); return fail(CALIB_E_HIP, hipGetErrorString(e)); }
         if (std::chrono::steady_clock::now() > deadline) {
             giveUp();
@@ -1302,22 +1333,22 @@ int calib_peer_prepare(calib_handle_t h, int nranks, int rank, void* out_handle6
     // device's L2 (uncached; fine-grained where the runtime has no uncached pool).
     const size_t bytes = (size_t)nranks * 2 * kPeerStride * 2 * sizeof(unsigned long long);
     void* mem = nullptr;
-    hipError_t e = hipExtMallocWithFlags(&mem, bytes, hipDeviceMallocUncached);
-    if (e != hipSuccess) {
+    if (hipExtMallocWithFlags(&mem, bytes, hipDeviceMallocUncached) != hipSuccess) {
         (void)hipGetLastError();
-        e = hipExtMallocWithFlags(&mem, bytes, hipDeviceMallocFinegrained);
+        const hipError_t e = hipExtMallocWithFlags(&mem, bytes, hipDeviceMallocFinegrained);
+        if (e != hipSuccess) return fail(CALIB_E_HIP, std::string("peer slot memory: ") + hipGetErrorString(e));
     }
-    if (e != hipSuccess) return fail(CALIB_E_HIP, std::string("peer slot memory: ") + hipGetErrorString(e));
     h->peer_mem = mem;
     h->peer_world = nranks;
     h->peer_rank = rank;
-    auto undo = [&](int code, const std::string& msg) { peer_release(h); return fail(code, msg); };
-    e = hipMemset(mem, 0, bytes);          // epoch 0 is never sent
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return undo(CALIB_E_HIP, std::string("peer slot memory: ") + hipGetErrorString(e));
+    auto undo = [&](const char* what, hipError_t e) {
+        peer_release(h);
+        return fail(CALIB_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    };
+    if (hipError_t e = hipMemset(mem, 0, bytes)) return undo("peer slot memory", e);          // epoch 0 is never sent
+    if (hipError_t e = hipDeviceSynchronize()) return undo("peer slot memory", e);
     hipIpcMemHandle_t ipc;
-    e = hipIpcGetMemHandle(&ipc, mem);
-    if (e != hipSuccess) return undo(CALIB_E_HIP, std::string("hipIpcGetMemHandle: ") + hipGetErrorString(e));
+    if (hipError_t e = hipIpcGetMemHandle(&ipc, mem)) return undo("hipIpcGetMemHandle", e);
     std::memcpy(out_handle64, &ipc, sizeof(ipc));
     {
         std::lock_guard<std::mutex> lock(g_local_slots_mutex);
@@ -1411,14 +1442,9 @@ int calib_peer_shutdown(calib_handle_t h) {
 int calib_lm_end(calib_handle_t h, double* P_out, double* out_sse, int* out_iters, double* out_trace) {
     CHECK_H(h);
     if (!h->lm_active) return fail(CALIB_E_STATE, "no LM run active");
-    SYNC_H(h);
     LMState s;
-    HIP_TRY(hipMemcpy(&s, st_cur(h), sizeof(s), hipMemcpyDeviceToHost));
-    h->lm_active = false;
-    const int prc = peer_fault_check(h);
-    if (prc) return prc;
-    if (s.error == CALIB_E_SINGULAR)
-        return fail(CALIB_E_SINGULAR, "Singular matrix: damped normal equations are not invertible");
+    const int rc = lm_finish(h, &s);
+    if (rc) return rc;
     // after the bootstrap round cur points at the current parameters
     const int cur = s.round == 0 ? 0 : s.cur;
     if (P_out) HIP_TRY(hipMemcpy(P_out, h->P[cur].p, (size_t)numParams(h) * 8, hipMemcpyDeviceToHost));
@@ -1445,14 +1471,9 @@ int calib_lm_step_delta(calib_handle_t h, const double* P, double lambda, double
     if (rc) return rc;
     rc = calib_lm_run(h, 1, 0);     // bootstrap round: evaluates P, solves, writes P + delta
     if (rc) return rc;
-    SYNC_H(h);
     LMState s;
-    HIP_TRY(hipMemcpy(&s, st_cur(h), sizeof(s), hipMemcpyDeviceToHost));
-    h->lm_active = false;
-    const int prc = peer_fault_check(h);
-    if (prc) return prc;
-    if (s.error == CALIB_E_SINGULAR)
-        return fail(CALIB_E_SINGULAR, "Singular matrix: damped normal equations are not invertible");
+    rc = lm_finish(h, &s);
+    if (rc) return rc;
     const int64_t K = numParams(h);
     std::vector<double> cand((size_t)K);
     HIP_TRY(hipMemcpy(cand.data(), h->P[s.cur ^ 1].p, (size_t)K * 8, hipMemcpyDeviceToHost));
@@ -1486,11 +1507,9 @@ int calib_normal_eq(calib_handle_t h, const double* P, double* out_B, double* ou
             std::fill(blk, blk + kGStride, 0.0);
             for (int it = vi0[v]; it < vi0[v + 1]; ++it)
                 for (int i = 0; i < kGStride; ++i) blk[i] += G[(size_t)it * kGStride + i];
-            if (sm.share > 0) {                 // stream form: the part of the view summed by a second wave
-                const int64_t first = (int64_t)v * sm.n4, w = (first + sm.n4 - 1) / sm.share;
-                if (w * sm.share > first)
-                    for (int i = 0; i < kGStride; ++i) blk[i] += G[(size_t)(sm.nv + w) * kGStride + i];
-            }
+            const int extra = stream_extra_item(sm, v);     // stream form: the part of the view summed by a second wave
+            if (extra >= 0)
+                for (int i = 0; i < kGStride; ++i) blk[i] += G[(size_t)extra * kGStride + i];
             for (int a = 0; a < 6; ++a) {
                 if (out_g) out_g[L + 6 * (int64_t)v + a] = blk[gvSlot(L, a)];
                 for (int b = 0; b < 6; ++b)     // V is symmetric; the record holds its lower triangle (g_v rides in the upper)
@@ -1505,111 +1524,45 @@ int calib_normal_eq(calib_handle_t h, const double* P, double* out_B, double* ou
 
 int calib_distort_points(int model, int64_t n, const double* x_norm, const double* k, double* out_xd) {
     if (n < 0 || (n > 0 && (!x_norm || !out_xd)) || !k) return fail(CALIB_E_INVALID, "null argument");
-    if (model != CALIB_MODEL_RADTAN && model != CALIB_MODEL_FISHEYE)
-        return fail(CALIB_E_INVALID, "unknown distortion model");
+    if (!known_model(model)) return fail(CALIB_E_INVALID, "unknown distortion model");
     if (n == 0) return CALIB_OK;
-    const int nk = model == CALIB_MODEL_RADTAN ? 5 : 4;
+    const int nk = num_distortion(model);
     DevBuf<double> dx, dk, dout;
     HIP_TRY(dx.alloc((size_t)n * 2)); HIP_TRY(dk.alloc(nk)); HIP_TRY(dout.alloc((size_t)n * 2));
     HIP_TRY(hipMemcpy(dx.p, x_norm, (size_t)n * 16, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dk.p, k, (size_t)nk * 8, hipMemcpyHostToDevice));
     const unsigned blocks = (unsigned)((n + 255) / 256);
-    if (model == CALIB_MODEL_RADTAN)
-        hipLaunchKernelGGL((distort_points_kernel<kRadtan>), dim3(blocks), dim3(256), 0, 0, dx.p, dk.p, n, dout.p);
-    else
-        hipLaunchKernelGGL((distort_points_kernel<kFisheye>), dim3(blocks), dim3(256), 0, 0, dx.p, dk.p, n, dout.p);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(out_xd, dout.p, (size_t)n * 16, hipMemcpyDeviceToHost);
-    dx.release(); dk.release(); dout.release();
-    if (e != hipSuccess) return fail(CALIB_E_HIP, hipGetErrorString(e));
+    const int rc = dispatch_model(model, [&](auto form) -> int {
+        hipLaunchKernelGGL((distort_points_kernel<decltype(form)::MODEL>), dim3(blocks), dim3(256), 0, 0, dx.p, dk.p, n, dout.p);
+        LAUNCHED(kNoHandle, "distort_points_kernel");
+        return CALIB_OK;
+    });
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(out_xd, dout.p, (size_t)n * 16, hipMemcpyDeviceToHost));
     return CALIB_OK;
 }
 
 int calib_project_with_distortion(int model, int64_t n, const double* A, const double* cam_xyz,
                                   const double* k, double* out_uv) {
     if (n < 0 || (n > 0 && (!cam_xyz || !out_uv)) || !k || !A) return fail(CALIB_E_INVALID, "null argument");
-    if (model != CALIB_MODEL_RADTAN && model != CALIB_MODEL_FISHEYE)
-        return fail(CALIB_E_INVALID, "unknown distortion model");
+    if (!known_model(model)) return fail(CALIB_E_INVALID, "unknown distortion model");
     if (n == 0) return CALIB_OK;
-    const int nk = model == CALIB_MODEL_RADTAN ? 5 : 4;
+    const int nk = num_distortion(model);
     DevBuf<double> dA, dc, dk, dout;
     HIP_TRY(dA.alloc(9)); HIP_TRY(dc.alloc((size_t)n * 3)); HIP_TRY(dk.alloc(nk)); HIP_TRY(dout.alloc((size_t)n * 2));
     HIP_TRY(hipMemcpy(dA.p, A, 72, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dc.p, cam_xyz, (size_t)n * 24, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dk.p, k, (size_t)nk * 8, hipMemcpyHostToDevice));
     const unsigned blocks = (unsigned)((n + 255) / 256);
-    if (model == CALIB_MODEL_RADTAN)
-        hipLaunchKernelGGL((project_cam_kernel<kRadtan>), dim3(blocks), dim3(256), 0, 0, dA.p, dc.p, dk.p, n, dout.p);
-    else
-        hipLaunchKernelGGL((project_cam_kernel<kFisheye>), dim3(blocks), dim3(256), 0, 0, dA.p, dc.p, dk.p, n, dout.p);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(out_uv, dout.p, (size_t)n * 16, hipMemcpyDeviceToHost);
-    dA.release(); dc.release(); dk.release(); dout.release();
-    if (e != hipSuccess) return fail(CALIB_E_HIP, hipGetErrorString(e));
-    return CALIB_OK;
-}
-
-namespace {
-
-int check_views(int64_t num_views, const int64_t* view_offsets, const double* sensor_uv, const double* model_xyz) {
-    if (num_views < 0 || !view_offsets) return fail(CALIB_E_INVALID, "null argument");
-    if (num_views == 0) return CALIB_OK;
-    const int64_t MN = view_offsets[num_views];
-    if (view_offsets[0] != 0 || MN < 0 || (MN > 0 && (!sensor_uv || !model_xyz)))
-        return fail(CALIB_E_INVALID, "bad view_offsets / point arrays");
-    for (int64_t i = 0; i < num_views; ++i)
-        if (view_offsets[i + 1] < view_offsets[i]) return fail(CALIB_E_INVALID, "view_offsets must be non-decreasing");
-    return CALIB_OK;
-}
-
-int use_device(int device_id) {
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (device_id < 0 || device_id >= ndev) return fail(CALIB_E_HIP, "no such HIP device (no CPU fallback)");
-    HIP_TRY(hipSetDevice(device_id));
-    return CALIB_OK;
-}
-
-// DLT and / or LM polish of every view's homography
-int homography_pipeline(int64_t num_views, const int64_t* view_offsets, const double* sensor_uv,
-                        const double* model_xyz, double* H, bool dlt, int refine_iters, int device_id) {
-    if (!H) return fail(CALIB_E_INVALID, "null argument");
-    int rc = check_views(num_views, view_offsets, sensor_uv, model_xyz);
-    if (rc || num_views == 0) return rc;
-    rc = use_device(device_id);
+    const int rc = dispatch_model(model, [&](auto form) -> int {
+        hipLaunchKernelGGL((project_cam_kernel<decltype(form)::MODEL>), dim3(blocks), dim3(256), 0, 0, dA.p, dc.p, dk.p, n, dout.p);
+        LAUNCHED(kNoHandle, "project_cam_kernel");
+        return CALIB_OK;
+    });
     if (rc) return rc;
-    const int64_t MN = view_offsets[num_views];
-    std::vector<double> xy((size_t)MN * 2);
-    for (int64_t p = 0; p < MN; ++p) { xy[2 * p] = model_xyz[3 * p]; xy[2 * p + 1] = model_xyz[3 * p + 1]; }
-    DevBuf<int64_t> doffs;
-    DevBuf<double> duv, dxy, dH;
-    hipError_t e = doffs.alloc((size_t)num_views + 1);
-    if (e == hipSuccess) e = duv.alloc((size_t)std::max<int64_t>(MN, 1) * 2);
-    if (e == hipSuccess) e = dxy.alloc((size_t)std::max<int64_t>(MN, 1) * 2);
-    if (e == hipSuccess) e = dH.alloc((size_t)num_views * 9);
-    if (e == hipSuccess) e = hipMemcpy(doffs.p, view_offsets, ((size_t)num_views + 1) * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess && MN) e = hipMemcpy(duv.p, sensor_uv, (size_t)MN * 16, hipMemcpyHostToDevice);
-    if (e == hipSuccess && MN) e = hipMemcpy(dxy.p, xy.data(), (size_t)MN * 16, hipMemcpyHostToDevice);
-    if (e == hipSuccess && !dlt) e = hipMemcpy(dH.p, H, (size_t)num_views * 72, hipMemcpyHostToDevice);
-    const unsigned blocks = (unsigned)((num_views + 15) / 16);
-    if (e == hipSuccess && dlt) {
-        hipLaunchKernelGGL(dlt_kernel, dim3(blocks), dim3(256), 0, 0, doffs.p, reinterpret_cast<const double2*>(duv.p),
-                           reinterpret_cast<const double2*>(dxy.p), num_views, dH.p);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && refine_iters > 0) {
-        hipLaunchKernelGGL(homography_lm_kernel, dim3(blocks), dim3(256), 0, 0, doffs.p,
-                           reinterpret_cast<const double2*>(duv.p), reinterpret_cast<const double2*>(dxy.p),
-                           num_views, refine_iters, dH.p);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(H, dH.p, (size_t)num_views * 72, hipMemcpyDeviceToHost);
-    doffs.release(); duv.release(); dxy.release(); dH.release();
-    if (e != hipSuccess) return fail(CALIB_E_HIP, hipGetErrorString(e));
+    HIP_TRY(hipMemcpy(out_uv, dout.p, (size_t)n * 16, hipMemcpyDeviceToHost));
     return CALIB_OK;
 }
-
-}  // namespace
 
 int calib_refine_homographies(int64_t num_views, const int64_t* view_offsets, const double* sensor_uv,
                               const double* model_xyz, double* H_inout, int max_iters, int device_id) {
@@ -1629,49 +1582,44 @@ int calib_refine_poses(int model, int64_t num_views, const int64_t* view_offsets
                        const double* model_xyz, const double* shared, double* poses_inout, int max_iters,
                        double lam_init, double lam_min, double lam_max, double err_min, double* out_sse,
                        int* out_iters, int* out_status, int device_id) {
-    if (model != CALIB_MODEL_RADTAN && model != CALIB_MODEL_FISHEYE)
-        return fail(CALIB_E_INVALID, "unknown distortion model");
+    if (!known_model(model)) return fail(CALIB_E_INVALID, "unknown distortion model");
     if (max_iters <= 0) return fail(CALIB_E_INVALID, "max_iters must be >= 1");
     if (!shared || (num_views > 0 && !poses_inout)) return fail(CALIB_E_INVALID, "null argument");
     int rc = check_views(num_views, view_offsets, sensor_uv, model_xyz);
     if (rc || num_views == 0) return rc;
     rc = use_device(device_id);
     if (rc) return rc;
-    const int L = model == CALIB_MODEL_RADTAN ? 10 : 9;
+    const int L = 5 + num_distortion(model);
     const int64_t MN = view_offsets[num_views];
     const size_t M = (size_t)num_views;
     DevBuf<int64_t> doffs;
-    DevBuf<double> duv, dxyz, dshared, dposes, dsse;
+    DevBuf<double2> duv;
+    DevBuf<double> dxyz, dshared, dposes, dsse;
     DevBuf<int> dint;             // iterations [0, M), status [M, 2 M)
-    hipError_t e = doffs.alloc(M + 1);
-    if (e == hipSuccess) e = duv.alloc((size_t)std::max<int64_t>(MN, 1) * 2);
-    if (e == hipSuccess) e = dxyz.alloc((size_t)std::max<int64_t>(MN, 1) * 3);
-    if (e == hipSuccess) e = dshared.alloc((size_t)L);
-    if (e == hipSuccess) e = dposes.alloc(M * 6);
-    if (e == hipSuccess) e = dsse.alloc(M);
-    if (e == hipSuccess) e = dint.alloc(2 * M);
-    if (e == hipSuccess) e = hipMemcpy(doffs.p, view_offsets, (M + 1) * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess && MN) e = hipMemcpy(duv.p, sensor_uv, (size_t)MN * 16, hipMemcpyHostToDevice);
-    if (e == hipSuccess && MN) e = hipMemcpy(dxyz.p, model_xyz, (size_t)MN * 24, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dshared.p, shared, (size_t)L * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dposes.p, poses_inout, M * 48, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        const dim3 grid((unsigned)((num_views + 15) / 16)), block(256);
-        const double2* uv2 = reinterpret_cast<const double2*>(duv.p);
-        if (model == CALIB_MODEL_RADTAN)
-            hipLaunchKernelGGL((pose_lm_kernel<kRadtan>), grid, block, 0, 0, doffs.p, uv2, dxyz.p, dshared.p, num_views,
-                               max_iters, lam_init, lam_min, lam_max, err_min, dposes.p, dsse.p, dint.p, dint.p + M);
-        else
-            hipLaunchKernelGGL((pose_lm_kernel<kFisheye>), grid, block, 0, 0, doffs.p, uv2, dxyz.p, dshared.p, num_views,
-                               max_iters, lam_init, lam_min, lam_max, err_min, dposes.p, dsse.p, dint.p, dint.p + M);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(poses_inout, dposes.p, M * 48, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out_sse) e = hipMemcpy(out_sse, dsse.p, M * 8, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out_iters) e = hipMemcpy(out_iters, dint.p, M * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out_status) e = hipMemcpy(out_status, dint.p + M, M * 4, hipMemcpyDeviceToHost);
-    doffs.release(); duv.release(); dxyz.release(); dshared.release(); dposes.release(); dsse.release(); dint.release();
-    if (e != hipSuccess) return fail(CALIB_E_HIP, hipGetErrorString(e));
+    HIP_TRY(doffs.alloc(M + 1));
+    HIP_TRY(duv.alloc((size_t)std::max<int64_t>(MN, 1)));
+    HIP_TRY(dxyz.alloc((size_t)std::max<int64_t>(MN, 1) * 3));
+    HIP_TRY(dshared.alloc((size_t)L));
+    HIP_TRY(dposes.alloc(M * 6));
+    HIP_TRY(dsse.alloc(M));
+    HIP_TRY(dint.alloc(2 * M));
+    HIP_TRY(hipMemcpy(doffs.p, view_offsets, (M + 1) * 8, hipMemcpyHostToDevice));
+    if (MN) HIP_TRY(hipMemcpy(duv.p, sensor_uv, (size_t)MN * 16, hipMemcpyHostToDevice));
+    if (MN) HIP_TRY(hipMemcpy(dxyz.p, model_xyz, (size_t)MN * 24, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dshared.p, shared, (size_t)L * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dposes.p, poses_inout, M * 48, hipMemcpyHostToDevice));
+    rc = dispatch_model(model, [&](auto form) -> int {
+        hipLaunchKernelGGL((pose_lm_kernel<decltype(form)::MODEL>), dim3((unsigned)((num_views + 15) / 16)), dim3(256), 0, 0,
+                           doffs.p, (const double2*)duv.p, dxyz.p, dshared.p, num_views, max_iters, lam_init, lam_min, lam_max,
+                           err_min, dposes.p, dsse.p, dint.p, dint.p + M);
+        LAUNCHED(kNoHandle, "pose_lm_kernel");
+        return CALIB_OK;
+    });
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(poses_inout, dposes.p, M * 48, hipMemcpyDeviceToHost));
+    if (out_sse) HIP_TRY(hipMemcpy(out_sse, dsse.p, M * 8, hipMemcpyDeviceToHost));
+    if (out_iters) HIP_TRY(hipMemcpy(out_iters, dint.p, M * 4, hipMemcpyDeviceToHost));
+    if (out_status) HIP_TRY(hipMemcpy(out_status, dint.p + M, M * 4, hipMemcpyDeviceToHost));
     return CALIB_OK;
 }
 
@@ -1687,7 +1635,7 @@ int calib_homography_jacobian(int64_t n, const double* h9, const double* model_x
     HIP_TRY(hipMemcpy(dh.p, h9, 72, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dx.p, model_xyz, (size_t)n * 24, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(homography_jacobian_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dh.p, dx.p, n, dJ.p);
-    LAUNCHED(static_cast<calib_handle_s*>(nullptr), "homography_jacobian_kernel");
+    LAUNCHED(kNoHandle, "homography_jacobian_kernel");
     HIP_TRY(hipMemcpy(out_J, dJ.p, (size_t)n * 18 * 8, hipMemcpyDeviceToHost));
     return CALIB_OK;
 }
@@ -1702,30 +1650,25 @@ int calib_compute_extrinsics(int64_t num_views, const double* A, const double* H
     if (!(a != 0.0) || !(b != 0.0)) return fail(CALIB_E_SINGULAR, "Singular matrix: intrinsic matrix is not invertible");
     const double Ainv[9] = {1.0 / a, -g / (a * b), (g * vc - uc * b) / (a * b), 0.0, 1.0 / b, -vc / b, 0.0, 0.0, 1.0};
     DevBuf<double> dA, dH, dW;
-    hipError_t e = dA.alloc(9);
-    if (e == hipSuccess) e = dH.alloc((size_t)num_views * 9);
-    if (e == hipSuccess) e = dW.alloc((size_t)num_views * 16);
-    if (e == hipSuccess) e = hipMemcpy(dA.p, Ainv, 72, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dH.p, H, (size_t)num_views * 72, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(extrinsics_kernel, dim3((unsigned)((num_views + 255) / 256)), dim3(256), 0, 0, dA.p, dH.p,
-                           num_views, dW.p);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(W_out, dW.p, (size_t)num_views * 128, hipMemcpyDeviceToHost);
-    dA.release(); dH.release(); dW.release();
-    if (e != hipSuccess) return fail(CALIB_E_HIP, hipGetErrorString(e));
+    HIP_TRY(dA.alloc(9));
+    HIP_TRY(dH.alloc((size_t)num_views * 9));
+    HIP_TRY(dW.alloc((size_t)num_views * 16));
+    HIP_TRY(hipMemcpy(dA.p, Ainv, 72, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dH.p, H, (size_t)num_views * 72, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(extrinsics_kernel, dim3((unsigned)((num_views + 255) / 256)), dim3(256), 0, 0, dA.p, dH.p, num_views, dW.p);
+    LAUNCHED(kNoHandle, "extrinsics_kernel");
+    HIP_TRY(hipMemcpy(W_out, dW.p, (size_t)num_views * 128, hipMemcpyDeviceToHost));
     return CALIB_OK;
 }
 
 int calib_distortion_normal_equations(int model, int64_t num_views, const int64_t* view_offsets,
                                       const double* sensor_uv, const double* model_xyz, const double* A,
                                       const double* W, double* out_DtD, double* out_Dtd, int device_id) {
-    if (model != CALIB_MODEL_RADTAN && model != CALIB_MODEL_FISHEYE) return fail(CALIB_E_INVALID, "unknown distortion model");
+    if (!known_model(model)) return fail(CALIB_E_INVALID, "unknown distortion model");
     if (!A || !out_DtD || !out_Dtd || (num_views > 0 && !W)) return fail(CALIB_E_INVALID, "null argument");
     int rc = check_views(num_views, view_offsets, sensor_uv, model_xyz);
     if (rc) return rc;
-    const int nk = model == CALIB_MODEL_RADTAN ? 5 : 4;
+    const int nk = num_distortion(model);
     const int ns = nk * (nk + 1) / 2 + nk;
     std::fill(out_DtD, out_DtD + nk * nk, 0.0);
     std::fill(out_Dtd, out_Dtd + nk, 0.0);
@@ -1739,34 +1682,31 @@ int calib_distortion_normal_equations(int model, int64_t num_views, const int64_
         for (int64_t p = view_offsets[v]; p < view_offsets[v + 1]; ++p) pv[(size_t)p] = (int)v;
     for (int64_t p = 0; p < MN; ++p) { xy[2 * p] = model_xyz[3 * p]; xy[2 * p + 1] = model_xyz[3 * p + 1]; z[p] = model_xyz[3 * p + 2]; }
     const int blocks = (int)std::min<int64_t>(1024, (MN + 255) / 256);
-    DevBuf<double> dA, dW, duv, dxy, dz, dpart;
+    DevBuf<double> dA, dW, dz, dpart;
+    DevBuf<double2> duv, dxy;
     DevBuf<int> dpv;
-    hipError_t e = dA.alloc(9);
-    if (e == hipSuccess) e = dW.alloc((size_t)num_views * 16);
-    if (e == hipSuccess) e = duv.alloc((size_t)MN * 2);
-    if (e == hipSuccess) e = dxy.alloc((size_t)MN * 2);
-    if (e == hipSuccess) e = dz.alloc((size_t)MN);
-    if (e == hipSuccess) e = dpv.alloc((size_t)MN);
-    if (e == hipSuccess) e = dpart.alloc((size_t)blocks * ns);
-    if (e == hipSuccess) e = hipMemcpy(dA.p, A, 72, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dW.p, W, (size_t)num_views * 128, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(duv.p, sensor_uv, (size_t)MN * 16, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dxy.p, xy.data(), (size_t)MN * 16, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dz.p, z.data(), (size_t)MN * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dpv.p, pv.data(), (size_t)MN * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        if (model == CALIB_MODEL_RADTAN)
-            hipLaunchKernelGGL((distortion_normal_kernel<kRadtan>), dim3(blocks), dim3(256), 0, 0, dA.p, dW.p, dpv.p,
-                               reinterpret_cast<const double2*>(duv.p), reinterpret_cast<const double2*>(dxy.p), dz.p, MN, dpart.p);
-        else
-            hipLaunchKernelGGL((distortion_normal_kernel<kFisheye>), dim3(blocks), dim3(256), 0, 0, dA.p, dW.p, dpv.p,
-                               reinterpret_cast<const double2*>(duv.p), reinterpret_cast<const double2*>(dxy.p), dz.p, MN, dpart.p);
-        e = hipGetLastError();
-    }
+    HIP_TRY(dA.alloc(9));
+    HIP_TRY(dW.alloc((size_t)num_views * 16));
+    HIP_TRY(duv.alloc((size_t)MN));
+    HIP_TRY(dxy.alloc((size_t)MN));
+    HIP_TRY(dz.alloc((size_t)MN));
+    HIP_TRY(dpv.alloc((size_t)MN));
+    HIP_TRY(dpart.alloc((size_t)blocks * ns));
+    HIP_TRY(hipMemcpy(dA.p, A, 72, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dW.p, W, (size_t)num_views * 128, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(duv.p, sensor_uv, (size_t)MN * 16, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dxy.p, xy.data(), (size_t)MN * 16, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dz.p, z.data(), (size_t)MN * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dpv.p, pv.data(), (size_t)MN * 4, hipMemcpyHostToDevice));
+    rc = dispatch_model(model, [&](auto form) -> int {
+        hipLaunchKernelGGL((distortion_normal_kernel<decltype(form)::MODEL>), dim3(blocks), dim3(256), 0, 0, dA.p, dW.p, dpv.p,
+                           (const double2*)duv.p, (const double2*)dxy.p, dz.p, MN, dpart.p);
+        LAUNCHED(kNoHandle, "distortion_normal_kernel");
+        return CALIB_OK;
+    });
+    if (rc) return rc;
     std::vector<double> part((size_t)blocks * ns);
-    if (e == hipSuccess) e = hipMemcpy(part.data(), dpart.p, part.size() * 8, hipMemcpyDeviceToHost);
-    dA.release(); dW.release(); duv.release(); dxy.release(); dz.release(); dpv.release(); dpart.release();
-    if (e != hipSuccess) return fail(CALIB_E_HIP, hipGetErrorString(e));
+    HIP_TRY(hipMemcpy(part.data(), dpart.p, part.size() * 8, hipMemcpyDeviceToHost));
     std::vector<double> sum((size_t)ns, 0.0);
     for (int bidx = 0; bidx < blocks; ++bidx)
         for (int j = 0; j < ns; ++j) sum[(size_t)j] += part[(size_t)bidx * ns + j];
@@ -1777,13 +1717,9 @@ int calib_distortion_normal_equations(int model, int64_t num_views, const int64_
     return CALIB_OK;
 }
 
-namespace {
-int num_distortion(int model) { return model == CALIB_MODEL_RADTAN ? 5 : 4; }
-}
-
 int calib_compose_params(int model, int64_t num_views, const double* A, const double* W, const double* k,
                          double* P_out, int device_id) {
-    if (model != CALIB_MODEL_RADTAN && model != CALIB_MODEL_FISHEYE) return fail(CALIB_E_INVALID, "unknown distortion model");
+    if (!known_model(model)) return fail(CALIB_E_INVALID, "unknown distortion model");
     if (num_views < 0 || !A || !k || !P_out || (num_views > 0 && !W)) return fail(CALIB_E_INVALID, "null argument");
     const int nk = num_distortion(model), L = 5 + nk;
     // shared part: (alpha, beta, gamma, uc, vc, k...) from A = [[alpha, gamma, uc], [0, beta, vc], [0, 0, 1]]
@@ -1797,14 +1733,14 @@ int calib_compose_params(int model, int64_t num_views, const double* A, const do
     HIP_TRY(dP.alloc((size_t)L + 6 * (size_t)num_views));
     HIP_TRY(hipMemcpy(dW.p, W, (size_t)num_views * 128, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(compose_views_kernel, dim3((unsigned)((num_views + 255) / 256)), dim3(256), 0, 0, dW.p, num_views, L, dP.p);
-    LAUNCHED(static_cast<calib_handle_s*>(nullptr), "compose_views_kernel");
+    LAUNCHED(kNoHandle, "compose_views_kernel");
     HIP_TRY(hipMemcpy(P_out + L, dP.p + L, (size_t)num_views * 48, hipMemcpyDeviceToHost));
     return CALIB_OK;
 }
 
 int calib_decompose_params(int model, int64_t num_views, const double* P, double* A_out, double* W_out,
                            double* k_out, int device_id) {
-    if (model != CALIB_MODEL_RADTAN && model != CALIB_MODEL_FISHEYE) return fail(CALIB_E_INVALID, "unknown distortion model");
+    if (!known_model(model)) return fail(CALIB_E_INVALID, "unknown distortion model");
     if (num_views < 0 || !P || (num_views > 0 && !W_out)) return fail(CALIB_E_INVALID, "null argument");
     const int nk = num_distortion(model), L = 5 + nk;
     if (A_out) {
@@ -1820,7 +1756,7 @@ int calib_decompose_params(int model, int64_t num_views, const double* P, double
     HIP_TRY(dP.alloc((size_t)L + 6 * (size_t)num_views));
     HIP_TRY(hipMemcpy(dP.p, P, ((size_t)L + 6 * (size_t)num_views) * 8, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(decompose_views_kernel, dim3((unsigned)((num_views + 255) / 256)), dim3(256), 0, 0, dP.p, num_views, L, dW.p);
-    LAUNCHED(static_cast<calib_handle_s*>(nullptr), "decompose_views_kernel");
+    LAUNCHED(kNoHandle, "decompose_views_kernel");
     HIP_TRY(hipMemcpy(W_out, dW.p, (size_t)num_views * 128, hipMemcpyDeviceToHost));
     return CALIB_OK;
 }
@@ -1873,79 +1809,6 @@ int calib_profile_read(calib_handle_t h, int which, double* out_total_ms, int64_
     return CALIB_OK;
 }
 
-}  // extern "C"
-// ---- uncertainty: per-view reprojection errors, parameter covariance -------------------------------------
-namespace {
-template <int MODEL, typename T>
-int launch_view_errors_t(calib_handle_s* h) {
-    using T2 = typename Pair<T>::type;
-    const unsigned blocks = (unsigned)((h->M + kViewErrWaves - 1) / kViewErrWaves);
-    hipLaunchKernelGGL((view_errors_kernel<MODEL, T>), dim3(blocks), dim3(64 * kViewErrWaves), 0, h->stream,
-                       (const double*)h->Peval.p, reinterpret_cast<const T2*>(h->uv.p), reinterpret_cast<const T2*>(h->XY.p),
-                       reinterpret_cast<const T*>(h->Z.p), reinterpret_cast<const T*>(h->VC.p), (const int*)h->pt_view.p,
-                       (const int64_t*)h->ext_offsets_dev.p, h->M, h->view_err.p);
-    LAUNCHED(h, "view_errors_kernel");
-    return CALIB_OK;
-}
-
-template <int L>
-int launch_covariance_views(calib_handle_s* h, double sigma2, bool cross) {
-    const int blocks = std::max(1, std::min((h->nv + kSchurThreads - 1) / kSchurThreads, 4 * h->num_cus));
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kSchurThreads), 0, h->stream, (const double*)h->G[0].p, view_items(h),
-                           (const int*)h->view_ext.p, h->nv, stream_map(h), (const double*)h->cov_css.p, sigma2,
-                           h->cov_views.p, cross ? h->cov_cross.p : nullptr, h->cov_flag.p);
-    };
-    if (h->plan.stream()) launch(covariance_views_kernel<L, true>); else launch(covariance_views_kernel<L, false>);
-    LAUNCHED(h, "covariance_views_kernel");
-    return CALIB_OK;
-}
-
-// sigma2 (S_free)^-1 of the reduced system S = Bsum - Ssub, zero-padded to L x L for the fixed parameters: Cholesky of
-// the free sub-matrix (lower triangle), its inverse by substitution, mirrored so that the result is exactly symmetric.
-// Pure host arithmetic on the all-reduced buffer: every rank of a sharded run gets the same bits.
-bool shared_covariance(const double* red, int L, uint32_t fixed_mask, double sigma2, double* Css /* L*L */) {
-    int idx[kMaxL], n = 0;
-    for (int i = 0; i < L; ++i) if (!((fixed_mask >> i) & 1)) idx[n++] = i;
-    double S[kMaxL][kMaxL], X[kMaxL][kMaxL];
-    for (int a = 0; a < n; ++a)
-        for (int b = 0; b <= a; ++b) S[a][b] = red[idx[a] * L + idx[b]] - red[L * L + idx[a] * L + idx[b]];
-    for (int j = 0; j < n; ++j) {                        // S = Lc Lc^T, in place
-        double d = S[j][j];
-        for (int q = 0; q < j; ++q) d -= S[j][q] * S[j][q];
-        if (!(d > 0.0)) return false;
-        S[j][j] = std::sqrt(d);
-        for (int i = j + 1; i < n; ++i) {
-            double t = S[i][j];
-            for (int q = 0; q < j; ++q) t -= S[i][q] * S[j][q];
-            S[i][j] = t / S[j][j];
-        }
-    }
-    for (int c = 0; c < n; ++c) {                        // column c of the inverse
-        double z[kMaxL];
-        for (int i = 0; i < n; ++i) {
-            double t = i == c ? 1.0 : 0.0;
-            for (int q = 0; q < i; ++q) t -= S[i][q] * z[q];
-            z[i] = t / S[i][i];
-        }
-        for (int i = n - 1; i >= 0; --i) {
-            double t = z[i];
-            for (int q = i + 1; q < n; ++q) t -= S[q][i] * X[q][c];
-            X[i][c] = t / S[i][i];
-        }
-    }
-    std::fill(Css, Css + L * L, 0.0);
-    for (int a = 0; a < n; ++a)
-        for (int b = 0; b <= a; ++b) {
-            const double v = sigma2 * X[a][b];
-            Css[idx[a] * L + idx[b]] = v;
-            Css[idx[b] * L + idx[a]] = v;
-        }
-    return true;
-}
-}  // namespace
-extern "C" {
-
 int calib_view_errors(calib_handle_t h, const double* P, double* out_view_sse, double* out_view_rms,
                       double* out_view_max) {
     CHECK_H(h);
@@ -1963,12 +1826,20 @@ int calib_view_errors(calib_handle_t h, const double* P, double* out_view_sse, d
     }
     HIP_TRY(h->view_err.alloc((size_t)M * 3));
     HIP_TRY(hipMemcpyAsync(h->Peval.p, P, (size_t)numParams(h) * 8, hipMemcpyHostToDevice, h->stream));
-    rc = launch_view_setup_any(h, h->Peval.p, nullptr, h->st_eval.p, 0);
+    rc = launch_view_setup(h, h->Peval.p, nullptr, h->st_eval.p, 0);
     if (rc) return rc;
-    if (h->dtype == CALIB_DTYPE_F64)
-        rc = h->model == CALIB_MODEL_RADTAN ? launch_view_errors_t<kRadtan, double>(h) : launch_view_errors_t<kFisheye, double>(h);
-    else
-        rc = h->model == CALIB_MODEL_RADTAN ? launch_view_errors_t<kRadtan, float>(h) : launch_view_errors_t<kFisheye, float>(h);
+    rc = dispatch(h, [&](auto form) -> int {
+        using F = decltype(form);
+        using T = typename F::T;
+        using T2 = typename F::T2;
+        const unsigned blocks = (unsigned)((M + kViewErrWaves - 1) / kViewErrWaves);
+        hipLaunchKernelGGL((view_errors_kernel<F::MODEL, T>), dim3(blocks), dim3(64 * kViewErrWaves), 0, h->stream,
+                           (const double*)h->Peval.p, h->uv_as<const T2>(), h->XY_as<const T2>(), h->Z_as<const T>(),
+                           h->VC_as<const T>(), (const int*)h->pt_view.p, (const int64_t*)h->ext_offsets_dev.p, M,
+                           h->view_err.p);
+        LAUNCHED(h, "view_errors_kernel");
+        return CALIB_OK;
+    });
     if (rc) return rc;
     std::vector<double> tmp((size_t)M * 3);
     HIP_TRY(hipMemcpyAsync(tmp.data(), h->view_err.p, tmp.size() * 8, hipMemcpyDeviceToHost, h->stream));
@@ -2028,8 +1899,18 @@ int calib_cov_finish(calib_handle_t h, int64_t total_points, int64_t total_views
     if (out_cov_cross) HIP_TRY(h->cov_cross.alloc((size_t)M * L * 6));
     HIP_TRY(hipMemcpyAsync(h->cov_css.p, Css, (size_t)L * L * 8, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemsetAsync(h->cov_flag.p, 0, sizeof(int), h->stream));
-    const int rc = L == 10 ? launch_covariance_views<10>(h, sigma2, out_cov_cross != nullptr)
-                           : launch_covariance_views<9>(h, sigma2, out_cov_cross != nullptr);
+    const int rc = dispatch(h, [&](auto form) -> int {
+        constexpr int LL = decltype(form)::L;
+        const int blocks = std::max(1, std::min((h->nv + kSchurThreads - 1) / kSchurThreads, 4 * h->num_cus));
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kSchurThreads), 0, h->stream, (const double*)h->G[0].p, view_items(h),
+                               (const int*)h->view_ext.p, h->nv, stream_map(h), (const double*)h->cov_css.p, sigma2,
+                               h->cov_views.p, out_cov_cross ? h->cov_cross.p : nullptr, h->cov_flag.p);
+        };
+        if (h->plan.stream()) launch(covariance_views_kernel<LL, true>); else launch(covariance_views_kernel<LL, false>);
+        LAUNCHED(h, "covariance_views_kernel");
+        return CALIB_OK;
+    });
     if (rc) return rc;
     int flag = 0;
     HIP_TRY(hipMemcpyAsync(&flag, h->cov_flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
@@ -2053,6 +1934,5 @@ int calib_covariance(calib_handle_t h, const double* P, double* out_sigma2, int6
     if (rc) return rc;
     return calib_cov_finish(h, h->MN, h->M, out_sigma2, out_dof, out_cov_shared, out_cov_views, out_cov_cross, out_std);
 }
-
 
 }  // extern "C"

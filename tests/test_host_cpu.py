@@ -271,3 +271,139 @@ def test_record_emission_tables_cover_every_read_entry_once(tmp_path):
     # ... and stream_extra_item (which overflow record holds the rest of a view cut by a wave start) agrees with a
     # direct simulation of the cuts on a few thousand (groups per view, views, waves) combinations
     assert "wave cuts:" in out.stdout and out.stdout.rstrip().endswith("ok")
+
+
+def _rejectedCalls():
+    """(function, arguments, expected code) of calls the library rejects -- or answers -- before its first device call"""
+    import ctypes
+    dp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    ip = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+    INV, OK, RT, FE = nat.E_INVALID, 0, nat.MODEL_RADTAN, nat.MODEL_FISHEYE
+    keep = []                               # the arrays behind the pointers live as long as the table
+
+    def arr(values, dtype=np.float64):
+        keep.append(np.ascontiguousarray(values, dtype=dtype))
+        return keep[-1]
+    offs, offs1, offsDec, offs3, offs0 = (ip(arr(o, np.int64)) for o in ([0, 4, 8], [1, 4, 8], [0, 5, 3], [0, 3, 7], [0]))
+    uv, xyz, x2, out2, cam = dp(arr(np.zeros((8, 2)))), dp(arr(np.zeros((8, 3)))), dp(arr(np.zeros((2, 2)))), dp(arr(np.zeros((2, 2)))), dp(arr(np.zeros((2, 3))))
+    A, k5, H, W, h9 = dp(arr(np.eye(3))), dp(arr(np.zeros(5))), dp(arr(np.zeros((2, 9)))), dp(arr(np.zeros((2, 16)))), dp(arr(np.ones(9)))
+    J, shared, poses, P = dp(arr(np.zeros((2, 18)))), dp(arr(np.ones(10))), dp(arr(np.zeros((2, 6)))), dp(arr(np.zeros(22)))
+    DtD, Dtd = dp(arr(np.zeros(25))), dp(arr(np.zeros(5)))
+    handle = ctypes.pointer(ctypes.c_void_p())
+    lm = (5, 1e-3, 1e-9, 1e9, 0.0)          # max_iters, lam_init, lam_min, lam_max, err_min
+    rows = [
+        ("calib_device_count", (None,), INV),
+        ("calib_create", (RT, nat.DTYPE_F64, 0, None), INV),
+        ("calib_create", (7, nat.DTYPE_F64, 0, handle), INV),                   # unknown model
+        ("calib_create", (-1, nat.DTYPE_F64, 0, handle), INV),
+        ("calib_create", (RT, 9, 0, handle), INV),                              # unknown dtype
+        ("calib_create", (FE, -1, 0, handle), INV),
+        ("calib_distort_points", (RT, -1, x2, k5, out2), INV),
+        ("calib_distort_points", (RT, 2, None, k5, out2), INV),
+        ("calib_distort_points", (RT, 2, x2, None, out2), INV),
+        ("calib_distort_points", (RT, 0, x2, None, out2), INV),                 # k is needed even for no points
+        ("calib_distort_points", (RT, 2, x2, k5, None), INV),
+        ("calib_distort_points", (7, 2, x2, k5, out2), INV),
+        ("calib_distort_points", (7, 0, x2, k5, out2), INV),                    # the model is checked before n == 0 answers
+        ("calib_distort_points", (FE, 0, None, k5, None), OK),
+        ("calib_project_with_distortion", (RT, -1, A, cam, k5, out2), INV),
+        ("calib_project_with_distortion", (RT, 2, None, cam, k5, out2), INV),
+        ("calib_project_with_distortion", (RT, 2, A, None, k5, out2), INV),
+        ("calib_project_with_distortion", (RT, 2, A, cam, None, out2), INV),
+        ("calib_project_with_distortion", (RT, 2, A, cam, k5, None), INV),
+        ("calib_project_with_distortion", (7, 2, A, cam, k5, out2), INV),
+        ("calib_project_with_distortion", (RT, 0, A, None, k5, None), OK),
+        ("calib_refine_homographies", (2, offs, uv, xyz, None, 5, 0), INV),
+        ("calib_refine_homographies", (-1, offs, uv, xyz, H, 5, 0), INV),
+        ("calib_refine_homographies", (2, None, uv, xyz, H, 5, 0), INV),
+        ("calib_refine_homographies", (2, offs1, uv, xyz, H, 5, 0), INV),       # view_offsets[0] != 0
+        ("calib_refine_homographies", (2, offsDec, uv, xyz, H, 5, 0), INV),     # decreasing offsets
+        ("calib_refine_homographies", (2, offs, None, xyz, H, 5, 0), INV),
+        ("calib_refine_homographies", (2, offs, uv, None, H, 5, 0), INV),
+        ("calib_refine_homographies", (0, offs0, None, None, H, 5, 0), OK),
+        ("calib_estimate_homographies", (2, offs3, uv, xyz, H, 5, 0), INV),     # a view with 3 points
+        ("calib_estimate_homographies", (2, offs, uv, xyz, None, 5, 0), INV),
+        ("calib_estimate_homographies", (-1, offs, uv, xyz, H, 5, 0), INV),
+        ("calib_estimate_homographies", (2, None, uv, xyz, H, 5, 0), INV),
+        ("calib_estimate_homographies", (2, offs, None, xyz, H, 5, 0), INV),
+        ("calib_estimate_homographies", (0, offs0, None, None, H, 0, 0), OK),
+        ("calib_refine_poses", (7, 2, offs, uv, xyz, shared, poses, *lm, None, None, None, 0), INV),
+        ("calib_refine_poses", (RT, 2, offs, uv, xyz, shared, poses, 0, *lm[1:], None, None, None, 0), INV),   # max_iters = 0
+        ("calib_refine_poses", (RT, 2, offs, uv, xyz, None, poses, *lm, None, None, None, 0), INV),
+        ("calib_refine_poses", (RT, 2, offs, uv, xyz, shared, None, *lm, None, None, None, 0), INV),
+        ("calib_refine_poses", (RT, -1, offs, uv, xyz, shared, poses, *lm, None, None, None, 0), INV),
+        ("calib_refine_poses", (RT, 2, None, uv, xyz, shared, poses, *lm, None, None, None, 0), INV),
+        ("calib_refine_poses", (RT, 2, offs1, uv, xyz, shared, poses, *lm, None, None, None, 0), INV),
+        ("calib_refine_poses", (FE, 2, offsDec, uv, xyz, shared, poses, *lm, None, None, None, 0), INV),
+        ("calib_refine_poses", (RT, 2, offs, None, xyz, shared, poses, *lm, None, None, None, 0), INV),
+        ("calib_refine_poses", (RT, 2, offs, uv, None, shared, poses, *lm, None, None, None, 0), INV),
+        ("calib_refine_poses", (RT, 0, offs0, None, None, shared, None, *lm, None, None, None, 0), OK),
+        ("calib_homography_jacobian", (-1, h9, cam, J, 0), INV),
+        ("calib_homography_jacobian", (2, None, cam, J, 0), INV),
+        ("calib_homography_jacobian", (2, h9, None, J, 0), INV),
+        ("calib_homography_jacobian", (2, h9, cam, None, 0), INV),
+        ("calib_homography_jacobian", (0, h9, None, None, 0), OK),
+        ("calib_compute_extrinsics", (-1, A, H, W, 0), INV),
+        ("calib_compute_extrinsics", (2, None, H, W, 0), INV),
+        ("calib_compute_extrinsics", (2, A, None, W, 0), INV),
+        ("calib_compute_extrinsics", (2, A, H, None, 0), INV),
+        ("calib_compute_extrinsics", (0, A, None, None, 0), OK),
+        ("calib_distortion_normal_equations", (7, 2, offs, uv, xyz, A, W, DtD, Dtd, 0), INV),
+        ("calib_distortion_normal_equations", (RT, 2, offs, uv, xyz, None, W, DtD, Dtd, 0), INV),
+        ("calib_distortion_normal_equations", (RT, 2, offs, uv, xyz, A, None, DtD, Dtd, 0), INV),
+        ("calib_distortion_normal_equations", (RT, 2, offs, uv, xyz, A, W, None, Dtd, 0), INV),
+        ("calib_distortion_normal_equations", (RT, 2, offs, uv, xyz, A, W, DtD, None, 0), INV),
+        ("calib_distortion_normal_equations", (RT, -1, offs, uv, xyz, A, W, DtD, Dtd, 0), INV),
+        ("calib_distortion_normal_equations", (RT, 2, None, uv, xyz, A, W, DtD, Dtd, 0), INV),
+        ("calib_distortion_normal_equations", (RT, 2, offs1, uv, xyz, A, W, DtD, Dtd, 0), INV),
+        ("calib_distortion_normal_equations", (FE, 2, offsDec, uv, xyz, A, W, DtD, Dtd, 0), INV),
+        ("calib_distortion_normal_equations", (RT, 2, offs, None, xyz, A, W, DtD, Dtd, 0), INV),
+        ("calib_distortion_normal_equations", (RT, 2, offs, uv, None, A, W, DtD, Dtd, 0), INV),
+        ("calib_compose_params", (7, 2, A, W, k5, P, 0), INV),
+        ("calib_compose_params", (RT, -1, A, W, k5, P, 0), INV),
+        ("calib_compose_params", (RT, 2, None, W, k5, P, 0), INV),
+        ("calib_compose_params", (RT, 2, A, None, k5, P, 0), INV),
+        ("calib_compose_params", (RT, 2, A, W, None, P, 0), INV),
+        ("calib_compose_params", (RT, 2, A, W, k5, None, 0), INV),
+        ("calib_decompose_params", (7, 2, P, A, W, k5, 0), INV),
+        ("calib_decompose_params", (RT, -1, P, A, W, k5, 0), INV),
+        ("calib_decompose_params", (RT, 2, None, A, W, k5, 0), INV),
+        ("calib_decompose_params", (RT, 2, P, A, None, k5, 0), INV),
+    ]
+    return rows, keep
+
+
+def test_return_codes_of_calls_rejected_before_any_device_call():
+    """Every handle-less entry point and calib_create, through ctypes, with arguments the library rejects -- or, for
+    num_views = 0 / n = 0, answers -- before its first device call, so the table holds with and without a GPU.
+    The expected codes were recorded from the library as it was before its host side was given one error idiom."""
+    import ctypes
+    lib = nat.loadLibrary()
+    rows, keep = _rejectedCalls()
+    assert {r[0] for r in rows} >= {"calib_create", "calib_distort_points", "calib_project_with_distortion",
+                                    "calib_refine_homographies", "calib_estimate_homographies", "calib_refine_poses",
+                                    "calib_homography_jacobian", "calib_compute_extrinsics",
+                                    "calib_distortion_normal_equations", "calib_compose_params", "calib_decompose_params"}
+    got = [(name, i, getattr(lib, name)(*args)) for i, (name, args, _) in enumerate(rows)]
+    assert got == [(name, i, want) for i, (name, _, want) in enumerate(rows)]
+    assert nat.lastError()                                  # the last row was a rejection: it left its message
+
+    # num_views = 0 / no points: CALIB_OK, and the outputs documented as written are written
+    dp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    ip = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+    A = np.array([[800.0, 0.5, 320.0], [0.0, 810.0, 240.0], [0.0, 0.0, 1.0]])
+    for model, nk in ((nat.MODEL_RADTAN, 5), (nat.MODEL_FISHEYE, 4)):
+        k = np.arange(1.0, nk + 1)
+        P = np.full(5 + nk + 2, np.nan)
+        assert lib.calib_compose_params(model, 0, dp(A), None, dp(k), dp(P), 0) == 0
+        assert np.array_equal(P[:5 + nk], np.concatenate(([800.0, 810.0, 0.5, 320.0, 240.0], k))) and np.isnan(P[5 + nk:]).all()
+        A2, k2 = np.full((3, 3), np.nan), np.full(nk, np.nan)
+        assert lib.calib_decompose_params(model, 0, dp(P), dp(A2), None, dp(k2), 0) == 0
+        assert np.array_equal(A2, A) and np.array_equal(k2, k)
+        assert lib.calib_decompose_params(model, 0, dp(P), None, None, None, 0) == 0
+        for nviews, offs in ((0, [0]), (2, [0, 0, 0])):     # no views; views without points
+            DtD, Dtd = np.full(nk * nk + 1, np.nan), np.full(nk + 1, np.nan)
+            W = np.zeros((2, 16))
+            assert lib.calib_distortion_normal_equations(model, nviews, ip(np.array(offs, dtype=np.int64)), None, None,
+                                                         dp(A), dp(W), dp(DtD), dp(Dtd), 0) == 0
+            assert not DtD[:nk * nk].any() and not Dtd[:nk].any() and np.isnan(DtD[-1]) and np.isnan(Dtd[-1])
