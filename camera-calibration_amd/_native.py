@@ -17,10 +17,13 @@ DTYPE_F64, DTYPE_F32 = 0, 1
 E_INVALID, E_HIP, E_SINGULAR, E_STATE = -1, -2, -3, -4
 TRACE_HEADER = 5
 LM_FUSED, LM_TWO_KERNEL = 0, 1
+IMAGE_U8, IMAGE_F32 = 0, 1
 
 _c_double_p = ctypes.POINTER(ctypes.c_double)
 _c_int64_p = ctypes.POINTER(ctypes.c_int64)
 _c_int_p = ctypes.POINTER(ctypes.c_int)
+_c_int32_p = ctypes.POINTER(ctypes.c_int32)
+_c_float_p = ctypes.POINTER(ctypes.c_float)
 _h = ctypes.c_void_p
 
 # name -> (restype, argtypes); must list every symbol include/calib_lm.h declares
@@ -66,6 +69,13 @@ SIGNATURES = {
     "calib_distort_points": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p]),
     "calib_project_with_distortion": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, _c_double_p, _c_double_p,
                                                      _c_double_p, _c_double_p]),
+    "calib_undistort_points": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p,
+                                              _c_double_p, _c_double_p, _c_int32_p, ctypes.c_int]),
+    "calib_undistort_maps": (ctypes.c_int, [ctypes.c_int, _c_double_p, _c_double_p, _c_double_p, ctypes.c_int,
+                                            ctypes.c_int, _c_float_p, _c_float_p, ctypes.c_int]),
+    "calib_remap": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_float_p,
+                                   _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
+                                   ctypes.c_int]),
     "calib_refine_homographies": (ctypes.c_int, [ctypes.c_int64, _c_int64_p, _c_double_p, _c_double_p, _c_double_p,
                                                  ctypes.c_int, ctypes.c_int]),
     "calib_refine_poses": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, _c_int64_p, _c_double_p, _c_double_p, _c_double_p,
@@ -175,6 +185,11 @@ def dptr(a):
         return None
     assert a.dtype == np.float64 and a.flags["C_CONTIGUOUS"]
     return a.ctypes.data_as(_c_double_p)
+
+
+def f32ptr(a):
+    assert a.dtype == np.float32 and a.flags["C_CONTIGUOUS"]
+    return a.ctypes.data_as(_c_float_p)
 
 
 def i64ptr(a):

@@ -2,6 +2,7 @@
 // Owns device memory, packs correspondences to SoA, sequences the kernels of kernels.hpp.
 #include "../../include/calib_lm.h"
 #include "kernels.hpp"
+#include "undistort.hpp"
 #include "host_rows.hpp"
 #include "launch_plan.hpp"
 #include "shard_layout.hpp"
@@ -243,6 +244,39 @@ int dispatch_model(int model, F&& f) { return dispatch(model, CALIB_DTYPE_F64, f
 
 bool known_model(int model) { return model == CALIB_MODEL_RADTAN || model == CALIB_MODEL_FISHEYE; }
 int num_distortion(int model) { return model == CALIB_MODEL_RADTAN ? 5 : 4; }
+
+// ---- undistortion entry points' helpers ----------------------------------------------------
+// alpha, beta, gamma, uc, vc of a row-major (3,3) camera matrix; false when it cannot be inverted
+bool pinhole_of(const double* A, Pinhole& p) {
+    p.al = A[0]; p.ga = A[1]; p.uc = A[2]; p.be = A[4]; p.vc = A[5];
+    return p.al != 0.0 && p.be != 0.0;
+}
+
+template <typename T>
+int remap_typed(const void* src, int src_h, int src_w, int channels, const float* mapx, const float* mapy, int dst_h,
+                int dst_w, double border, void* dst) {
+    const size_t nsrc = (size_t)src_h * src_w * channels, npix = (size_t)dst_h * dst_w, ndst = npix * channels;
+    DevBuf<T> dsrc, ddst;
+    DevBuf<float> dmx, dmy;
+    HIP_TRY(dsrc.alloc(nsrc)); HIP_TRY(ddst.alloc(ndst)); HIP_TRY(dmx.alloc(npix)); HIP_TRY(dmy.alloc(npix));
+    HIP_TRY(hipMemcpy(dsrc.p, src, nsrc * sizeof(T), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dmx.p, mapx, npix * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dmy.p, mapy, npix * 4, hipMemcpyHostToDevice));
+    const dim3 grid((unsigned)((dst_h + kRemapRows - 1) / kRemapRows), (unsigned)((dst_w + 63) / 64)), block(64, kRemapRows);
+    auto launch = [&](auto c) -> int {
+        hipLaunchKernelGGL((remap_kernel<T, decltype(c)::value>), grid, block, 0, 0, (const T*)dsrc.p, src_h, src_w,
+                           (const float*)dmx.p, (const float*)dmy.p, dst_h, dst_w, (float)border, ddst.p);
+        LAUNCHED(kNoHandle, "remap_kernel");
+        return CALIB_OK;
+    };
+    const int rc = channels == 1 ? launch(std::integral_constant<int, 1>{})
+                 : channels == 2 ? launch(std::integral_constant<int, 2>{})
+                 : channels == 3 ? launch(std::integral_constant<int, 3>{})
+                                 : launch(std::integral_constant<int, 4>{});
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(dst, ddst.p, ndst * sizeof(T), hipMemcpyDeviceToHost));
+    return CALIB_OK;
+}
 
 // ---- RCCL, resolved at run time (calib_rccl_load) ------------------------------------------
 // Only the handful of entry points the one all-reduce needs; types as in rccl.h (ncclUniqueId is 128
@@ -839,7 +873,7 @@ bool shared_covariance(const double* red, int L, uint32_t fixed_mask, double sig
 // ============================================================================ C-ABI
 extern "C" {
 
-int calib_version(void) { return 420; }   // 4.2: calib_view_errors, calib_cov_local / calib_cov_finish / calib_covariance
+int calib_version(void) { return 430; }   // 4.3: calib_undistort_points, calib_undistort_maps, calib_remap
 
 const char* calib_last_error(void) { return g_err.c_str(); }
 
@@ -1933,6 +1967,95 @@ int calib_covariance(calib_handle_t h, const double* P, double* out_sigma2, int6
     const int rc = calib_cov_local(h, P);
     if (rc) return rc;
     return calib_cov_finish(h, h->MN, h->M, out_sigma2, out_dof, out_cov_shared, out_cov_views, out_cov_cross, out_std);
+}
+
+// ---- undistortion (undistort.hpp): the inverse model on points, the rectify maps, the bilinear remap -----------------
+int calib_undistort_points(int model, int64_t n, const double* A, const double* k, const double* uv,
+                           const double* newA, double* out_xy, int32_t* out_status, int device_id) {
+    if (n < 0 || (n > 0 && (!uv || !out_xy)) || !k || !A) return fail(CALIB_E_INVALID, "null argument");
+    if (!known_model(model)) return fail(CALIB_E_INVALID, "unknown distortion model");
+    Pinhole cam, out;
+    if (!pinhole_of(A, cam) || (newA && !pinhole_of(newA, out)))
+        return fail(CALIB_E_INVALID, "alpha and beta of a camera matrix must not be 0");
+    if (n == 0) return CALIB_OK;
+    int rc = use_device(device_id);
+    if (rc) return rc;
+    const int nk = num_distortion(model);
+    std::vector<double> xy((size_t)n * 2);                  // pixels -> distorted normalised points
+    for (int64_t i = 0; i < n; ++i) {
+        const double yd = (uv[2 * i + 1] - cam.vc) / cam.be;
+        xy[2 * i] = (uv[2 * i] - cam.uc - cam.ga * yd) / cam.al;
+        xy[2 * i + 1] = yd;
+    }
+    DevBuf<double2> din, dout;
+    DevBuf<double> dk;
+    DevBuf<int32_t> dstatus;
+    HIP_TRY(din.alloc((size_t)n)); HIP_TRY(dout.alloc((size_t)n)); HIP_TRY(dk.alloc(nk)); HIP_TRY(dstatus.alloc((size_t)n));
+    HIP_TRY(hipMemcpy(din.p, xy.data(), (size_t)n * 16, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dk.p, k, (size_t)nk * 8, hipMemcpyHostToDevice));
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    rc = dispatch_model(model, [&](auto form) -> int {
+        hipLaunchKernelGGL((undistort_points_kernel<decltype(form)::MODEL>), dim3(blocks), dim3(256), 0, 0,
+                           (const double2*)din.p, (const double*)dk.p, n, dout.p, dstatus.p);
+        LAUNCHED(kNoHandle, "undistort_points_kernel");
+        return CALIB_OK;
+    });
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(out_xy, dout.p, (size_t)n * 16, hipMemcpyDeviceToHost));
+    if (out_status) HIP_TRY(hipMemcpy(out_status, dstatus.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (newA)                                               // ideal normalised points -> pixels of the new camera
+        for (int64_t i = 0; i < n; ++i) {
+            const double x = out_xy[2 * i], y = out_xy[2 * i + 1];
+            out_xy[2 * i] = out.al * x + out.ga * y + out.uc;
+            out_xy[2 * i + 1] = out.be * y + out.vc;
+        }
+    return CALIB_OK;
+}
+
+int calib_undistort_maps(int model, const double* A, const double* k, const double* newA, int width, int height,
+                         float* out_mapx, float* out_mapy, int device_id) {
+    if (!A || !k || !out_mapx || !out_mapy) return fail(CALIB_E_INVALID, "null argument");
+    if (!known_model(model)) return fail(CALIB_E_INVALID, "unknown distortion model");
+    if (width <= 0 || height <= 0) return fail(CALIB_E_INVALID, "width and height must be positive");
+    if ((int64_t)width * height > (int64_t)INT32_MAX) return fail(CALIB_E_INVALID, "a map has at most 2^31 - 1 pixels");
+    Pinhole cam, dst;
+    if (!pinhole_of(A, cam) || !pinhole_of(newA ? newA : A, dst))
+        return fail(CALIB_E_INVALID, "alpha and beta of a camera matrix must not be 0");
+    int rc = use_device(device_id);
+    if (rc) return rc;
+    const int nk = num_distortion(model);
+    const unsigned total = (unsigned)width * (unsigned)height;
+    DevBuf<double> dk;
+    DevBuf<float> dmaps;                                    // mapx, then mapy from the next 16-byte boundary
+    const size_t plane = ((size_t)total + 3) / 4 * 4;
+    HIP_TRY(dk.alloc(nk)); HIP_TRY(dmaps.alloc(2 * plane));
+    HIP_TRY(hipMemcpy(dk.p, k, (size_t)nk * 8, hipMemcpyHostToDevice));
+    const unsigned perBlock = 256u * (unsigned)kMapCols;
+    const unsigned blocks = (unsigned)(((uint64_t)total + perBlock - 1) / perBlock);
+    rc = dispatch_model(model, [&](auto form) -> int {
+        hipLaunchKernelGGL((undistort_map_kernel<decltype(form)::MODEL>), dim3(blocks), dim3(256), 0, 0, cam, dst,
+                           (const double*)dk.p, (unsigned)width, total, dmaps.p, dmaps.p + plane);
+        LAUNCHED(kNoHandle, "undistort_map_kernel");
+        return CALIB_OK;
+    });
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(out_mapx, dmaps.p, (size_t)total * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_mapy, dmaps.p + plane, (size_t)total * 4, hipMemcpyDeviceToHost));
+    return CALIB_OK;
+}
+
+int calib_remap(int dtype, const void* src, int src_h, int src_w, int channels, const float* mapx, const float* mapy,
+                int dst_h, int dst_w, double border, void* dst, int device_id) {
+    if (!src || !mapx || !mapy || !dst) return fail(CALIB_E_INVALID, "null argument");
+    if (dtype != CALIB_IMAGE_U8 && dtype != CALIB_IMAGE_F32) return fail(CALIB_E_INVALID, "unknown image dtype");
+    if (channels < 1 || channels > 4) return fail(CALIB_E_INVALID, "an image has 1 to 4 channels");
+    if (src_h <= 0 || src_w <= 0 || dst_h <= 0 || dst_w <= 0) return fail(CALIB_E_INVALID, "image sizes must be positive");
+    if ((dst_w + 63) / 64 > 65535) return fail(CALIB_E_INVALID, "destination too wide (at most 4194240 columns)");
+    const int rc = use_device(device_id);
+    if (rc) return rc;
+    return dtype == CALIB_IMAGE_U8
+               ? remap_typed<uint8_t>(src, src_h, src_w, channels, mapx, mapy, dst_h, dst_w, border, dst)
+               : remap_typed<float>(src, src_h, src_w, channels, mapx, mapy, dst_h, dst_w, border, dst);
 }
 
 }  // extern "C"

@@ -44,6 +44,26 @@ class DistortionModel:
             raise ValueError(f"Expected shape (None, 2), got {x.shape}")
         return engine.distortPoints(self.modelId, x, self._checkK(k))
 
+    def undistortPoints(self, A, k, uv, newA=None, returnStatus=False):
+        """uv (N,2) pixels of the distorted image -> (N,2) ideal points: normalised (x, y), or pixels of the camera
+        matrix newA. The inverse of projectWithDistortion's distortion step, by Newton on the device. Where the model
+        has no inverse (past the turning point of its radial polynomial, a folded-over root, a non-finite pixel) the
+        row is NaN; returnStatus=True also returns the (N,) int32 status, 0 = solved, 1 = not."""
+        uv = np.asarray(uv, dtype=np.float64)
+        if uv.ndim != 2 or uv.shape[1] != 2:
+            raise ValueError(f"Expected shape (None, 2), got {uv.shape}")
+        xy, status = engine.undistortPoints(self.modelId, A, self._checkK(k), uv, newA)
+        return (xy, status) if returnStatus else xy
+
+    def undistortMaps(self, A, k, size, newA=None):
+        """size = (width, height) of the undistorted image -> (mapx, mapy), float32 (height, width): the position in
+        the distorted image that each pixel of the undistorted one (camera matrix newA, default A) shows."""
+        try:
+            width, height = size
+        except (TypeError, ValueError):
+            raise ValueError(f"size: expected (width, height), got {size!r}") from None
+        return engine.undistortMaps(self.modelId, A, self._checkK(k), width, height, newA)
+
     def estimateDistortion(self, A, allDetections, allBoardPosesInCamera, device=0):
         """Linear least-squares start value of k given A and the board poses (src/distortion.py:70,
         110-191 radial-tangential, 222-271 fisheye): D^T D and D^T Ddot are formed on the device

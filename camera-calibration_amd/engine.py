@@ -686,3 +686,82 @@ def projectWithDistortion(modelId, A, X, k):
     nat.check(nat.loadLibrary().calib_project_with_distortion(modelId, X.shape[0], nat.dptr(A), nat.dptr(X),
                                                               nat.dptr(k), nat.dptr(out)))
     return out
+
+
+# ---- undistortion (include/calib_lm.h, "undistortion"): every argument is checked before the library is touched --------
+def _cameraMatrix(A, name):
+    A = np.ascontiguousarray(A, dtype=np.float64)
+    if A.shape != (3, 3):
+        raise ValueError(f"{name}: expected shape (3, 3), got {A.shape}")
+    return A
+
+
+def _coefficients(modelId, k):
+    if modelId not in (nat.MODEL_RADTAN, nat.MODEL_FISHEYE):
+        raise ValueError(f"unknown distortion model {modelId!r}")
+    k = np.ascontiguousarray(k, dtype=np.float64).ravel()
+    n = 5 if modelId == nat.MODEL_RADTAN else 4
+    if k.shape[0] != n:
+        raise ValueError(f"k: expected {n} distortion coefficients, got {k.shape[0]}")
+    return k
+
+
+def undistortPoints(modelId, A, k, uv, newA=None, device=0):
+    """uv (N,2) pixels of the distorted image -> (xy (N,2), status (N,) int32): the ideal point of each pixel --
+    normalised, or in pixels of newA -- and 0 where it was found, 1 (xy NaN) where the model has no inverse there."""
+    uv = np.asarray(uv, dtype=np.float64)
+    if uv.ndim != 2 or uv.shape[1] != 2:
+        raise ValueError(f"uv: expected shape (None, 2), got {uv.shape}")
+    uv = np.ascontiguousarray(uv)
+    A, k = _cameraMatrix(A, "A"), _coefficients(modelId, k)
+    newA = None if newA is None else _cameraMatrix(newA, "newA")
+    xy = np.empty_like(uv)
+    status = np.empty(uv.shape[0], dtype=np.int32)
+    nat.requireDevice()
+    nat.check(nat.loadLibrary().calib_undistort_points(
+        modelId, uv.shape[0], nat.dptr(A), nat.dptr(k), nat.dptr(uv), nat.dptr(newA), nat.dptr(xy),
+        status.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(device)))
+    return xy, status
+
+
+def undistortMaps(modelId, A, k, width, height, newA=None, device=0):
+    """(mapx, mapy), float32 (height, width): where pixel (row, col) of the undistorted image (camera newA, default A)
+    lies in the distorted one -- what remap takes."""
+    width, height = int(width), int(height)
+    if width <= 0 or height <= 0:
+        raise ValueError(f"size: width and height must be positive, got ({width}, {height})")
+    A, k = _cameraMatrix(A, "A"), _coefficients(modelId, k)
+    newA = None if newA is None else _cameraMatrix(newA, "newA")
+    mapx = np.empty((height, width), dtype=np.float32)
+    mapy = np.empty((height, width), dtype=np.float32)
+    nat.requireDevice()
+    nat.check(nat.loadLibrary().calib_undistort_maps(modelId, nat.dptr(A), nat.dptr(k), nat.dptr(newA), width, height,
+                                                     nat.f32ptr(mapx), nat.f32ptr(mapy), int(device)))
+    return mapx, mapy
+
+
+def remap(image, mapx, mapy, border=0.0, device=0):
+    """image (H, W, C) uint8 or float32, 1 <= C <= 4; mapx, mapy (h, w) float32 -> (h, w, C) of the image's dtype:
+    bilinear samples at (mapx, mapy), taps outside the image = border."""
+    image = np.asarray(image)
+    if image.ndim != 3 or not 1 <= image.shape[2] <= 4 or image.shape[0] < 1 or image.shape[1] < 1:
+        raise ValueError(f"image: expected shape (H, W, C) with 1 <= C <= 4, got {image.shape}")
+    if image.dtype == np.uint8:
+        dtype = nat.IMAGE_U8
+    elif image.dtype == np.float32:
+        dtype = nat.IMAGE_F32
+    else:
+        raise ValueError(f"image: expected dtype uint8 or float32, got {image.dtype}")
+    mapx, mapy = np.asarray(mapx), np.asarray(mapy)
+    if mapx.ndim != 2 or mapx.shape != mapy.shape or mapx.size == 0:
+        raise ValueError(f"maps: expected two arrays of one shape (h, w), got {mapx.shape} and {mapy.shape}")
+    if mapx.dtype != np.float32 or mapy.dtype != np.float32:
+        raise ValueError(f"maps: expected dtype float32, got {mapx.dtype} and {mapy.dtype}")
+    image, mapx, mapy = np.ascontiguousarray(image), np.ascontiguousarray(mapx), np.ascontiguousarray(mapy)
+    h, w = mapx.shape
+    out = np.empty((h, w, image.shape[2]), dtype=image.dtype)
+    nat.requireDevice()
+    nat.check(nat.loadLibrary().calib_remap(dtype, image.ctypes.data_as(ctypes.c_void_p), image.shape[0], image.shape[1],
+                                            image.shape[2], nat.f32ptr(mapx), nat.f32ptr(mapy), h, w, float(border),
+                                            out.ctypes.data_as(ctypes.c_void_p), int(device)))
+    return out

@@ -287,6 +287,42 @@ int calib_distort_points(int model, int64_t n, const double* x_norm, const doubl
 int calib_project_with_distortion(int model, int64_t n, const double* A, const double* cam_xyz,
                                   const double* k, double* out_uv);
 
+/* ---- undistortion: the inverse of the camera model, rectify maps, image remap -----------------------------------
+ * Surface beside the drop-in one (the reference runs its model forward only). Stateless: no handle, host pointers, the
+ * work runs on device_id. A and newA are (3,3) row-major, A = [[alpha, gamma, uc], [0, beta, vc], [0, 0, 1]]; k is the
+ * model's coefficient vector (5 radtan | 4 fisheye). alpha or beta equal to 0, in A or in newA, is CALIB_E_INVALID.
+ *
+ * calib_undistort_points: uv (n,2) pixels of the distorted image -> out_xy (n,2), the IDEAL point of each: normalised
+ *   (x, y) when newA is NULL, else the pixel newA (x, y, 1). A pixel becomes the distorted normalised point
+ *   yd = (v - vc) / beta, xd = (u - uc - gamma yd) / alpha, and distort(x, y) = (xd, yd) is solved by Newton in fp64
+ *   with the model's own 2 x 2 Jacobian (radtan) or in one dimension on theta (fisheye, which is radial; theta_d < 1e-8
+ *   returns (xd, yd), the forward model's r -> 0 limit). At most 30 iterations; an iteration stops at a step of 4 ulp of
+ *   max(1, |x|). out_status (n) or NULL, per point:
+ *     0  solved: |distort(x, y) - (xd, yd)|_inf <= 64 * 2^-52 * max(1, |(xd, yd)|_inf) AND the model preserves
+ *        orientation at (x, y) -- radtan: its Jacobian is positive definite; fisheye: d theta_d / d theta > 0 and
+ *        theta < pi / 2. This is the root on the branch that contains the optical axis.
+ *     1  not solved, out_xy is NaN: the target has no preimage (past the turning point of the radial polynomial), the
+ *        iteration ended on a folded-over branch, or the input is not finite. The call itself still returns CALIB_OK.
+ *   n == 0 is CALIB_OK.
+ * calib_undistort_maps: the maps an undistorted image of width x height pixels and camera matrix newA (NULL: A itself,
+ *   gamma kept) reads from: destination pixel (col j, row i) looks along y = (i - vc') / beta',
+ *   x = (j - uc' - gamma' y) / alpha' and finds it in the source at (mapx, mapy)(i, j) = A distort(x, y). Evaluated in
+ *   fp64, STORED AS FP32 (rounded to nearest), two (height, width) planes: half a ulp of fp32 is 3e-5 px at 1000 px.
+ *   width * height < 2^31.
+ * calib_remap: dst (dst_h, dst_w, channels) = src (src_h, src_w, channels; interleaved, 1 <= channels <= 4) sampled
+ *   bilinearly at (mapx, mapy) (dst_h, dst_w), fp32 arithmetic: x0 = floor(sx), fx = sx - x0, likewise y, taps a (y0, x0),
+ *   b (y0, x0 + 1), c (y0 + 1, x0), d (y0 + 1, x0 + 1); top = a + fx (b - a), bot = c + fx (d - c), out = top + fy (bot - top).
+ *   A TAP outside the source takes the constant `border` (the pixel's other taps still count; nothing is clamped or
+ *   reflected), and a map entry that is NaN or infinite yields `border`. CALIB_IMAGE_U8: rint (ties to even), saturated to
+ *   [0, 255]; CALIB_IMAGE_F32: the fp32 value. src, dst and the maps must not overlap. */
+enum { CALIB_IMAGE_U8 = 0, CALIB_IMAGE_F32 = 1 };
+int calib_undistort_points(int model, int64_t n, const double* A, const double* k, const double* uv,
+                           const double* newA, double* out_xy, int32_t* out_status, int device_id);
+int calib_undistort_maps(int model, const double* A, const double* k, const double* newA, int width, int height,
+                         float* out_mapx, float* out_mapy, int device_id);
+int calib_remap(int dtype, const void* src, int src_h, int src_w, int channels, const float* mapx, const float* mapy,
+                int dst_h, int dst_w, double border, void* dst, int device_id);
+
 /* Per-view homography polish of the initialisation stage: Calibrator._refineHomographies
  * (src/calibrate.py:60-111, HomographyJacobian src/jacobian.py:88-121), all views in one launch.
  * H_inout (M,3,3) row-major: DLT homographies in, LM-refined (H[2,2] = 1) out. model_xyz (MN,3):
