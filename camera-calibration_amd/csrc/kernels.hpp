@@ -116,6 +116,12 @@ __device__ __forceinline__ float2 lane_gather(float2 v, int srcLane) {
     return o;
 }
 
+// `v` of lane `lane` (wave-uniform) as a scalar
+__device__ __forceinline__ double readlane_d(double v, int lane) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane),
+                            __builtin_amdgcn_readlane(__double2loint(v), lane));
+}
+
 struct LMState {
     double lam, err_cur, last_err, lam_min, lam_max, err_min;
     int cur;        // index of the buffers holding the current P / view blocks
@@ -387,6 +393,38 @@ constexpr int kFusedWaves = 4;                            // waves per workgroup
 // ---- what fused_kernel and fused_stream_kernel share: the wave's slab and the 4x4x4 block form of the contraction
 // A wave's private LDS slab for storage type T and C Jacobian columns: kFusedRows rows (points) of 16 chunks (columns,
 // one (u, v) pair each). After the main loop the same memory holds the wave's two accumulator tiles.
+// The two words of the LM state a fused launch needs -- the finished flag and the index of the current buffers --
+// requested where the kernel makes its other requests and taken up behind the last of them. sel 0 (explicit P0 / G0):
+// the state is not looked at. take() passes the words as they were loaded through an empty asm: tested inside request()'s
+// branch, they are a wait inside it, in front of everything requested later.
+struct StateWords {
+    int fin = 0, useP1 = 0;
+    __device__ __forceinline__ void request(const LMState* __restrict__ st, int sel) {
+        if (sel) { fin = st->done; useP1 = st->cur; }
+    }
+    __device__ __forceinline__ void take(int sel) {
+        asm("" : "+s"(fin), "+s"(useP1));
+        useP1 = sel ? useP1 ^ 1 : 0;                          // the candidate's buffers (selectP)
+    }
+};
+// The shared parameters of BOTH P buffers in one vector load: lanes 0..15 of each half wave hold P0's, lanes 16..31
+// P1's (sel 0: P0's again); the chosen buffer's go to scalar registers once the state is there. (Two sets of scalar
+// loads next to the view constants' are more scalar registers than a wave has: the compiler then splits the requests.)
+template <int L>
+__device__ __forceinline__ double request_shared_both(const double* __restrict__ P0, const double* __restrict__ P1,
+                                                      int sel, int lane) {
+    const int pl = lane & 15;
+    return (((lane & 16) && sel) ? P1 : P0)[pl < L ? pl : L - 1];
+}
+template <int MODEL, typename T>
+__device__ __forceinline__ void shared_from_lanes(Shared<MODEL, T>& sp, double pboth, int useP1) {
+    constexpr int L = ModelTraits<MODEL>::C - 6;
+    double pv[L];
+#pragma unroll
+    for (int j = 0; j < L; ++j) pv[j] = readlane_d(pboth, (useP1 ? 16 : 0) + j);
+    sp.load(pv);
+}
+
 template <typename T, int C>
 struct FusedSlab {
     using T2 = typename Pair<T>::type;
@@ -435,10 +473,19 @@ struct FusedSlab {
     static __device__ __forceinline__ double* tileU(T2* slab) { return reinterpret_cast<double*>(slab); }
     static __device__ __forceinline__ double* tileV(T2* slab) { return tileU(slab) + kEmitTile; }
     // the workgroup's partial of B, g_c, sum r^2 from the parked tiles of all its waves, in wave order, through the
-    // emit table (after the workgroup's barrier)
-    static __device__ __forceinline__ void writePartial(const unsigned char* smem, const uint32_t* emit_tab, double* part) {
+    // emit table (after the workgroup's barrier). The thread's table entry depends on nothing the kernel computes:
+    // partEntry asks for it before the tiles are parked, so that behind the barrier only LDS reads and the store remain.
+    // (the index passes through an empty asm: the request stays where it is written -- hoisted to the top of a kernel that
+    // makes it on two paths, the entry would hold a register through the whole main loop)
+    static __device__ __forceinline__ uint32_t partEntry(const uint32_t* __restrict__ emit_tab) {
+        uint32_t t = 0;
+        int i = kGStride + (int)threadIdx.x;
+        asm("" : "+v"(i));
+        if ((int)threadIdx.x < kPartStride) t = emit_tab[i];
+        return t;
+    }
+    static __device__ __forceinline__ void writePartial(const unsigned char* smem, uint32_t t, double* part) {
         if ((int)threadIdx.x < kPartStride) {
-            const uint32_t t = emit_tab[kGStride + threadIdx.x];
             const double* T0 = reinterpret_cast<const double*>(smem);
             double o = 0.0;
 #pragma unroll
@@ -518,8 +565,18 @@ __global__ __launch_bounds__(64 * kFusedWaves, (sizeof(T) == 4 ? (MULTI ? 5 : 6)
     constexpr int RS = Slab::RS, ROWS = Slab::ROWS, WAVES = Slab::WAVES, SLAB = Slab::SIZE;
     constexpr bool MF32 = Slab::MF32, RCOL = Slab::RCOL, ONES = Slab::ONES;
     __shared__ __attribute__((aligned(16))) unsigned char smem[Slab::BYTES];                // one slab per wave
-    if (sel && st->done) return;
-    const double* P = selectP(P0, P1, st, sel);
+    // As in fused_stream_kernel, nothing waits for the LM state that does not need it: the item's extent, its first
+    // points and the shared parameters of both P buffers are requested first, the state behind them, and the finished
+    // flag is tested before the first store to memory.
+    // (fp64 forms. The fp32 forms run 5-6 waves per SIMD in two or more rounds of workgroups, other waves cover the
+    // state's trip, and the cure measured slower there -- c4 shard 40.73 -> 40.91 us, every value above the parent's --
+    // so they read the state first, as before.)
+    StateWords sw;
+    if constexpr (MF32) {
+        sw.request(st, sel);
+        sw.take(sel);
+        if (sw.fin) return;
+    }
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lw = wpi == 4 ? 2 : (wpi == 2 ? 1 : 0);           // wpi is 1, 2 or 4: shifts, not divisions
@@ -540,7 +597,7 @@ __global__ __launch_bounds__(64 * kFusedWaves, (sizeof(T) == 4 ? (MULTI ? 5 : 6)
     // G44 (fp64 only): the Gram is built from 4x4 blocks by v_mfma_f64_4x4x4_4b instead; unused, and compiled away, in
     // the tile forms
     BlockAcc blk(lane);
-    double* Gbase = sel ? ((st->cur ^ 1) ? G1 : G0) : G0;
+    double* Gbase = (MF32 && sw.useP1) ? G1 : G0;               // fp64: chosen with the state, before the first record leaves
     // One wave per item (tile forms): the item's record goes to HBM straight from the accumulators (lane (k, c) holds
     // rows k + 4 reg -- 4 k + reg behind the fp32 MFMA -- of column c; 16 lanes store 128 contiguous bytes): rows
     // L..L+5 of J^T J but for the six slots that carry g_v, which the residual's row fills. No table, no LDS,
@@ -577,12 +634,26 @@ __global__ __launch_bounds__(64 * kFusedWaves, (sizeof(T) == 4 ? (MULTI ? 5 : 6)
         const int qbeg = sub * per;
         const int qend = qbeg + per < n ? qbeg + per : n;
         Shared<MODEL, T> sp;
-        sp.load(P);
-        Slab::initRows(slab, lane);
+        double pboth = 0.0;
+        if constexpr (MF32) {
+            sp.load(sw.useP1 ? P1 : P0);
+            Slab::initRows(slab, lane);
+        } else {
+            pboth = request_shared_both<C - 6>(P0, P1, sel, lane);
+        }
         // inputs of the next batch are requested before the current batch is evaluated
         int64_t pn = pbeg + (qbeg + sl < qend ? qbeg + sl : qend - 1);
         T2 m_n = uv[pn], xy_n = XY[pn];
         T z_n = Z[pn];
+        if constexpr (!MF32) {
+            sw.request(st, sel);
+            __builtin_amdgcn_sched_barrier(0);                // everything is requested; LDS is set up behind the requests
+            sw.take(sel);
+            Slab::initRows(slab, lane);
+            if (sw.fin) return;                               // the same for the whole grid; nothing has been stored
+            shared_from_lanes<MODEL, T>(sp, pboth, sw.useP1);
+            Gbase = sw.useP1 ? G1 : G0;
+        }
         for (;; ++item) {
         const T* vc = VC + (int64_t)__builtin_amdgcn_readfirstlane(uniform_n ? item : item_view[item]) * kViewStride;
         for (int q0 = qbeg; q0 < qend; q0 += 64) {
@@ -735,6 +806,11 @@ __global__ __launch_bounds__(64 * kFusedWaves, (sizeof(T) == 4 ? (MULTI ? 5 : 6)
         }
         pbeg += n;
         }
+    } else if constexpr (!MF32) {
+        sw.request(st, sel);
+        sw.take(sel);
+        if (sw.fin) return;
+        Gbase = sw.useP1 ? G1 : G0;
     }
     // Output assembly: every wave parks its two accumulator tiles (f64 MFMA C/D layout: col = lane & 15,
     // row = (lane >> 4) + 4 * reg; zeros for a wave without an item) in its dead slab; then the
@@ -742,6 +818,7 @@ __global__ __launch_bounds__(64 * kFusedWaves, (sizeof(T) == 4 ? (MULTI ? 5 : 6)
     // both from the index table -- no case analysis, 16-byte coalesced stores.
     double* TU = Slab::tileU(slab);
     double* TV = Slab::tileV(slab);
+    const uint32_t tpart = Slab::partEntry(emit_tab);
     if (!G44 && wpi == 1 && valid) emitDirect(item);            // the (last) item's record
     __builtin_amdgcn_wave_barrier();                            // the slab is this wave's own: no workgroup barrier needed yet
     if constexpr (!G44) {
@@ -757,7 +834,7 @@ __global__ __launch_bounds__(64 * kFusedWaves, (sizeof(T) == 4 ? (MULTI ? 5 : 6)
     }
     if (lane == 0) { TU[kEmitZero] = 0.0; TV[kEmitZero] = 0.0; }
     __syncthreads();
-    Slab::writePartial(smem, emit_tab, part);
+    Slab::writePartial(smem, tpart, part);
     if ((!G44 && wpi == 1) || sub != 0 || !valid) return;       // the item's first wave assembles the record from the parked tiles
     double* G = Gbase + (int64_t)item * kGStride;
     if (lane < kGStride / 2) {
@@ -871,13 +948,15 @@ __global__ __launch_bounds__(64 * kFusedWaves, kStreamMinBlocks) void fused_stre
     // requested from BOTH P buffers. So all of those are requested first and the state behind them (readState: its load
     // travels with theirs instead of ahead of them, as in reduce_kernel), and the finished flag is tested before the
     // first store to memory: a round enqueued after the end of the refinement still writes nothing.
-    int fin = 0, useP1 = 0;
-    auto readState = [&]() {
-        if (sel) {                                            // sel 0: explicit P0 / G0, the state is not looked at
-            fin = st->done;
-            useP1 = st->cur ^ 1;                              // the candidate's buffers (selectP)
-        }
-    };
+    // One wait for all of it: the kernel arguments the prologue reads are asked for together here (left to itself the
+    // compiler fetches each one in the block that first uses it, a trip of its own in front of every request), and the
+    // op table's copy into LDS comes behind the last request (a wait for the table in front of them was another).
+    // (not volatile and with no memory operand, so that the loads behind it stay scalar loads of memory nothing writes;
+    // kept alive and in the entry block by `share`, which passes through it and is used there. VC and st stay out of it:
+    // a pointer handed to an asm counts as captured, and the uniform loads through it -- the view constants', the
+    // state's -- would no longer be known unwritten and become vector loads: 36 VGPRs more in the main loop)
+    asm("" : "+s"(share) : "s"(P0), "s"(P1), "s"(uv), "s"(XY), "s"(Z), "s"(stream_ops), "s"(n), "s"(nv), "s"(sel));
+    StateWords sw;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int k = lane >> 4;
@@ -888,12 +967,6 @@ __global__ __launch_bounds__(64 * kFusedWaves, kStreamMinBlocks) void fused_stre
     auto ofView = [](int i) { return i >= L && i < L + 6; };
     const bool keep0 = !(ofView(blk.trow) || ofView(blk.tcol0)), keep1 = !(ofView(blk.trow) || ofView(blk.tcol1)),
                keep2 = !(ofView(blk.trow) || ofView(blk.tcol2));
-    // every wave writes the (same) whole table and every lane only ever reads back its own 24 bytes: no barrier
-    {
-        const int4* src = reinterpret_cast<const int4*>(stream_ops) + 3 * lane;
-        int4* dst = reinterpret_cast<int4*>(sops) + 3 * lane;
-        dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2];
-    }
     const int partner = blk.bj * 16 + ((blk.bi + 2) & 3) * 4 + k;       // holds the other rows' sums of this lane's (b, b+2) entry
     // the finished view's record, straight from the accumulators; then what belongs to a view restarts from zero
     // Every op is ONE buffer store with the lane's byte offset in the voffset: the record is a 1 KiB buffer resource, and
@@ -935,17 +1008,18 @@ __global__ __launch_bounds__(64 * kFusedWaves, kStreamMinBlocks) void fused_stre
     const int w = blockIdx.x * WAVES + wave;
     const long long gt = (long long)nv * n4, g0 = (long long)w * share;
     const bool valid = g0 < gt;
+    uint32_t tpart = 0;
     if (valid) {
         const int p0 = (int)(4 * g0);
         const int p1 = (int)(4 * (g0 + share < gt ? g0 + share : gt));
         int va = __builtin_amdgcn_readfirstlane(p0 / n);      // the view being accumulated
         int vend = (va + 1) * n;                              // its end = the next boundary, in points
         int slot = p0 != va * n ? nv + w : va;
-        Shared<MODEL, T> sp, spB;                              // spB: the other P buffer's, lives only in the prologue
-        sp.load(P0);
-        spB = sp;
-        if (sel) spB.load(P1);
-        Slab::initRows(slab, lane);
+        // every valid wave writes the (same) whole table and every lane only ever reads back its own 48 bytes: no
+        // barrier. Requested first, stored behind the prologue's other requests (vector loads return in order).
+        const int4* opsrc = reinterpret_cast<const int4*>(stream_ops) + 3 * lane;
+        const int4 op0 = opsrc[0], op1 = opsrc[1], op2 = opsrc[2];
+        const double pboth = request_shared_both<L>(P0, P1, sel, lane);      // both P buffers' shared parameters
         int pn = p0 + sl < p1 ? p0 + sl : p1 - 1;
         T2 m_n = uv[pn], xy_n = XY[pn];
         T z_n = Z[pn];
@@ -967,10 +1041,18 @@ __global__ __launch_bounds__(64 * kFusedWaves, kStreamMinBlocks) void fused_stre
         };
         bool strad = straddles(p0, vend);
         if (strad) vc_n = stagedLoad(va); else scalarLoad(va);
-        readState();
-        if (fin) return;                                      // the same for the whole workgroup; nothing has been stored
-        if (useP1) sp = spB;
-        Gbase = useP1 ? G1 : G0;
+        sw.request(st, sel);                                  // last: VC's address is fetched with a (short) wait of its own
+        __builtin_amdgcn_sched_barrier(0);                    // everything is requested; LDS is set up behind the requests
+        sw.take(sel);
+        {
+            int4* dst = reinterpret_cast<int4*>(sops) + 3 * lane;
+            dst[0] = op0; dst[1] = op1; dst[2] = op2;
+        }
+        Slab::initRows(slab, lane);
+        if (sw.fin) return;                                   // the same for the whole workgroup; nothing has been stored
+        Shared<MODEL, T> sp;
+        shared_from_lanes<MODEL, T>(sp, pboth, sw.useP1);
+        Gbase = sw.useP1 ? G1 : G0;
         const T2* src = slab + Slab::rowOff(k);                // rows 4 s + k: + 66 chunks per group
         const int c = lane & 15, c1 = (c + 4) & 15, c2 = (c + 8) & 15, jh = (lane >> 3) & 1;
         const T* h0 = reinterpret_cast<const T*>(src + c) + jh;
@@ -1137,10 +1219,13 @@ __global__ __launch_bounds__(64 * kFusedWaves, kStreamMinBlocks) void fused_stre
             }
         }
         // the share's last view (whole, or cut by the share's end)
+        tpart = Slab::partEntry(emit_tab);                    // for writePartial: in flight with the last record's stores
         emitView(slot);
     } else {
-        readState();
-        if (fin) return;
+        sw.request(st, sel);
+        tpart = emit_tab[kGStride + ((int)threadIdx.x < kPartStride ? (int)threadIdx.x : 0)];
+        sw.take(sel);
+        if (sw.fin) return;
     }
     // the workgroup's partial of B, g_c, sum r^2: every wave parks its block accumulators as the two full symmetric
     // 16 x 16 tiles in its (idle) slab; 112 threads add the four waves' entries through the index table
@@ -1152,7 +1237,7 @@ __global__ __launch_bounds__(64 * kFusedWaves, kStreamMinBlocks) void fused_stre
         if (lane == 0) { TU[kEmitZero] = 0.0; TV[kEmitZero] = 0.0; }
     }
     __syncthreads();
-    Slab::writePartial(smem, emit_tab, part);
+    Slab::writePartial(smem, tpart, part);
 }
 
 // ---------------------------------------------------------------- stream form: which records make up a view
@@ -1430,20 +1515,26 @@ __global__ __launch_bounds__(kSchurBlock, (!WIDE && STREAM) ? 3 : 4) void schur_
     // blockIdx.y = 0 / 1 is the BUFFER the block eliminates (G0 / G1), known at launch: the first views' heads
     // are requested before the LM state -- which says whether that buffer holds the candidate (variant A) or the
     // current blocks (variant B) -- has arrived, one memory latency instead of two dependent ones
+    // The four state words the layer needs are asked for in one go in front of the heads and taken up behind them (the
+    // empty asm: read where they are used -- behind the return, behind the boot branch -- each was a trip of its own
+    // after the heads had arrived).
     const double* G = blockIdx.y ? G1 : G0;
+    int st_done = st->done, st_cur = st->cur, st_round = st->round;
+    double st_lam = st->lam;
     double V[21], b[6];
     int v0 = blockIdx.x * kSchurViewsPerBlock;
     if (v0 + grp < nv) load_view_head<L, WIDE>(G, view_span<STREAM>(view_item0, sm, v0 + grp), c, V, b);
-    if (st->done) return;
-    const bool boot = st->round == 0;
-    const int cand = st->cur ^ 1;
+    asm("" : "+s"(st_done), "+s"(st_cur), "+s"(st_round), "+s"(st_lam));
+    if (st_done) return;
+    const bool boot = st_round == 0;
+    const int cand = st_cur ^ 1;
     const int variant = (int)blockIdx.y == cand ? 0 : 1;
     double* out = part + ((int64_t)variant * gridDim.x + blockIdx.x) * VA;
     if (variant == 1 && boot) {       // no "current" blocks yet
         for (int i = tid; i < VA; i += kSchurBlock) out[i] = 0.0;
         return;
     }
-    const double lam = variant == 0 ? (boot ? st->lam : st->lam / 10) : st->lam * 10;
+    const double lam = variant == 0 ? (boot ? st_lam : st_lam / 10) : st_lam * 10;
 
     d4 acc = {0.0, 0.0, 0.0, 0.0};
     double nfail = 0.0;
@@ -1604,6 +1695,7 @@ __global__ __launch_bounds__(64) void reduce_kernel(const double* __restrict__ p
     const int i = blockIdx.x, lane = threadIdx.x;
     const int variant = i / VA, idx = i - variant * VA;
     const double* src = part + (int64_t)variant * nblocks * VA + idx;
+    int st_done = st->done;                                   // requested with the partials, looked at behind the tree
     // all of a lane's loads are issued before the first add (a rolled load-wait-add loop made this
     // kernel a chain of up to 16 memory latencies); nblocks <= kMaxSchurBlocks = 16 x 64
     double v[kMaxSchurBlocks / 64];
@@ -1622,7 +1714,8 @@ __global__ __launch_bounds__(64) void reduce_kernel(const double* __restrict__ p
     // the finished flag is looked at only now: its load travels with the partials' instead of ahead of them.
     // A round that comes after the end of the loop still takes part in the exchange (with whatever it summed): the
     // epochs advance per ENQUEUED round on every rank, and two parities are only enough while every epoch is used
-    const bool done = st->done != 0;
+    asm("" : "+s"(st_done));                                  // (taken up here: not a load the compiler may move down)
+    const bool done = st_done != 0;
     if (x.world > 1) t = peer_sum(x, i, __shfl(t, 0, 64), lane);
     if (done) return;
     if (lane == 0) red[i] = t;
@@ -1749,10 +1842,6 @@ __device__ __forceinline__ bool gauss_jordan16(double (&row)[N + 1], int i, int&
 // kernel's 9-13 us). Every lane returns the whole solution. Returns false when a pivot is not
 // positive; the caller then falls back to gauss_jordan16 (same behaviour as before on such input).
 // Only valid in lanes 0..15 of a wave with the other lanes inactive.
-__device__ __forceinline__ double readlane_d(double v, int lane) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane),
-                            __builtin_amdgcn_readlane(__double2loint(v), lane));
-}
 
 template <int N>
 __device__ __forceinline__ bool spd_solve_wave0(double (&row)[N + 1], int i, double (&x)[N]) {
@@ -1833,10 +1922,17 @@ __device__ __forceinline__ bool lm_update_step(const LMState* __restrict__ in, L
         gA = red[2 * L * L + i];
         gS = in->gc[i];
     }
-    const double nfailA = red[kNfail], nfailB = red[VA + kNfail];
+    double nfailA = red[kNfail], nfailB = red[VA + kNfail];
+    // Every other state word the step can need travels with the requests above as well, and all of them are taken up
+    // here (the empty asm): read where the stop rule uses them, each was a load and a wait of its own between the
+    // branches of the decision, on the chain the rest of the workgroup waits for at its barrier.
+    int in_done = in->done, in_iters = in->iters, in_max_iters = in->max_iters, in_fixed_mask = in->fixed_mask;
+    double in_err_cur = in->err_cur, in_lam_min = in->lam_min, in_lam_max = in->lam_max, in_err_min = in->err_min;
+    asm("" : "+s"(in_done), "+s"(in_iters), "+s"(in_max_iters), "+s"(in_fixed_mask), "+s"(in_err_cur), "+s"(in_lam_min),
+             "+s"(in_lam_max), "+s"(in_err_min), "+s"(nfailA), "+s"(nfailB));
     // the finished flag is looked at only now: its load travels with the requests above instead of ahead of them
     // (a dependent round trip less in front of the solve; what was requested is dropped when the loop is over)
-    if (in->done) {                                  // keep the finished state visible to later rounds
+    if (in_done) {                                   // keep the finished state visible to later rounds
         if (writer) for (int j = i; j < (int)(sizeof(LMState) / 8); j += 16)
             reinterpret_cast<double*>(out)[j] = reinterpret_cast<const double*>(in)[j];
         return false;
@@ -1844,8 +1940,8 @@ __device__ __forceinline__ bool lm_update_step(const LMState* __restrict__ in, L
     bool useB = false;                               // the reject variant (current blocks, 10 lambda)
     bool done = false;
     double err_cur_new = err_cand, last_err = err_cand;
-    int iters = in->iters, accepted = 0;
-    const double err_cur = in->err_cur;
+    int iters = in_iters, accepted = 0;
+    const double err_cur = in_err_cur;
     const LMDecision dec = lm_decide(cur, lam, round, err_cand, err_cur);
     if (round > 0) {
         const int it = round - 1;
@@ -1855,7 +1951,7 @@ __device__ __forceinline__ bool lm_update_step(const LMState* __restrict__ in, L
             if (i == 0) { row[0] = it; row[1] = err_cur; row[2] = err_cand; row[3] = lam; row[4] = dec.acc ? 1.0 : 0.0; }
         }
         useB = !dec.acc;
-        done = !(in->lam_min < dec.lam && dec.lam < in->lam_max) || err_cur < in->err_min || it + 1 >= in->max_iters;
+        done = !(in_lam_min < dec.lam && dec.lam < in_lam_max) || err_cur < in_err_min || it + 1 >= in_max_iters;
         last_err = err_cur;                          // the reference returns the pre-update error (:155,171)
         err_cur_new = dec.acc ? err_cand : err_cur;
         iters = it + 1;
@@ -1885,7 +1981,7 @@ __device__ __forceinline__ bool lm_update_step(const LMState* __restrict__ in, L
     // so it is the reduced system that is edited: a fixed lane's row becomes the unit row with right-hand side 0 (dc
     // exactly 0), every other row loses its fixed columns. The mask is uniform, so mask 0 -- the default -- branches
     // round the selects: they sit on the one wave's chain in front of the solve (0.12 us of c2's 16.5 us round).
-    const int fixed_mask = in->fixed_mask;
+    const int fixed_mask = in_fixed_mask;
     const bool fixed_i = (fixed_mask >> i) & 1;
     if (fixed_mask != 0) {
 #pragma unroll
@@ -1924,11 +2020,16 @@ __device__ __forceinline__ bool lm_update_step(const LMState* __restrict__ in, L
         }
         if (w0) {
             out->lam = lam; out->err_cur = err_cur_new; out->last_err = last_err;
-            out->lam_min = in->lam_min; out->lam_max = in->lam_max; out->err_min = in->err_min;
-            out->cur = cur; out->round = round + 1; out->iters = iters; out->max_iters = in->max_iters;
+            // (what is only handed on is read again here, behind the solve and through a pointer of its own: held in
+            // registers from the top, it costs the small-shard kernel its fourth workgroup per CU)
+            const LMState* pass = in;
+            asm("" : "+s"(pass));
+            out->lam_min = pass->lam_min; out->lam_max = pass->lam_max; out->err_min = pass->err_min;
+            out->cur = cur; out->round = round + 1; out->iters = iters; out->max_iters = pass->max_iters;
             out->done = done ? 1 : 0; out->error = error; out->accepted_last = accepted; out->fixed_mask = fixed_mask;
-            out->notify = in->notify;
-            if (done && in->notify) __hip_atomic_store(in->notify, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            int* const notify = pass->notify;
+            out->notify = notify;
+            if (done && notify) __hip_atomic_store(notify, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
     cur_out = cur;
