@@ -26,6 +26,17 @@ _c_int32_p = ctypes.POINTER(ctypes.c_int32)
 _c_float_p = ctypes.POINTER(ctypes.c_float)
 _h = ctypes.c_void_p
 
+
+
+class StereoProblem(ctypes.Structure):
+    """calib_stereo_problem_t"""
+    _fields_ = [("model_a", ctypes.c_int), ("model_b", ctypes.c_int), ("num_views", ctypes.c_int64),
+                ("offs_a", _c_int64_p), ("uv_a", _c_double_p), ("xyz_a", _c_double_p), ("shared_a", _c_double_p),
+                ("offs_b", _c_int64_p), ("uv_b", _c_double_p), ("xyz_b", _c_double_p), ("shared_b", _c_double_p)]
+
+
+_stereo_p = ctypes.POINTER(StereoProblem)
+
 # name -> (restype, argtypes); must list every symbol include/calib_lm.h declares
 SIGNATURES = {
     "calib_version": (ctypes.c_int, []),
@@ -107,6 +118,12 @@ SIGNATURES = {
                                         _c_double_p, _c_double_p]),
     "calib_profile_enable": (ctypes.c_int, [_h, ctypes.c_int]),
     "calib_profile_read": (ctypes.c_int, [_h, ctypes.c_int, _c_double_p, _c_int64_p]),
+    "calib_stereo_normal_eq": (ctypes.c_int, [_stereo_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+                                              _c_double_p, ctypes.c_int]),
+    "calib_stereo_step_delta": (ctypes.c_int, [_stereo_p, _c_double_p, ctypes.c_double, _c_double_p, ctypes.c_int]),
+    "calib_refine_stereo": (ctypes.c_int, [_stereo_p, _c_double_p, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                           ctypes.c_double, ctypes.c_double, _c_double_p, _c_double_p, _c_int_p,
+                                           _c_double_p, ctypes.c_int]),
 }
 
 _lib = None

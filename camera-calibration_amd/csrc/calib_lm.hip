@@ -3,6 +3,7 @@
 #include "../../include/calib_lm.h"
 #include "kernels.hpp"
 #include "undistort.hpp"
+#include "stereo.hpp"
 #include "host_rows.hpp"
 #include "launch_plan.hpp"
 #include "shard_layout.hpp"
@@ -873,7 +874,7 @@ bool shared_covariance(const double* red, int L, uint32_t fixed_mask, double sig
 // ============================================================================ C-ABI
 extern "C" {
 
-int calib_version(void) { return 430; }   // 4.3: calib_undistort_points, calib_undistort_maps, calib_remap
+int calib_version(void) { return 440; }   // 4.4: calib_stereo_normal_eq, calib_stereo_step_delta, calib_refine_stereo
 
 const char* calib_last_error(void) { return g_err.c_str(); }
 
@@ -2056,6 +2057,237 @@ int calib_remap(int dtype, const void* src, int src_h, int src_w, int channels, 
     return dtype == CALIB_IMAGE_U8
                ? remap_typed<uint8_t>(src, src_h, src_w, channels, mapx, mapy, dst_h, dst_w, border, dst)
                : remap_typed<float>(src, src_h, src_w, channels, mapx, mapy, dst_h, dst_w, border, dst);
+}
+
+}  // extern "C"
+
+// ---- stereo calibration with both cameras known (stereo.hpp) ------------------------------------
+namespace {
+
+int check_stereo(const calib_stereo_problem_t* p, const double* Ps) {
+    if (!p || !Ps) return fail(CALIB_E_INVALID, "null argument");
+    if (!known_model(p->model_a) || !known_model(p->model_b)) return fail(CALIB_E_INVALID, "unknown distortion model");
+    if (p->num_views < 1) return fail(CALIB_E_INVALID, "stereo calibration needs at least one view");
+    if (!p->shared_a || !p->shared_b) return fail(CALIB_E_INVALID, "null argument");
+    const int rc = check_views(p->num_views, p->offs_a, p->uv_a, p->xyz_a);
+    return rc ? rc : check_views(p->num_views, p->offs_b, p->uv_b, p->xyz_b);
+}
+
+// Device side of one stereo call: the problem, the two (point, record, total) buffer sets the loop alternates between,
+// the state. Released with the scope of the entry point.
+struct StereoRun {
+    struct Cam {
+        DevBuf<int64_t> offs;
+        DevBuf<double2> uv;
+        DevBuf<double> xyz, shared;
+        StereoCam view() const { return StereoCam{offs.p, uv.p, xyz.p, shared.p}; }
+    };
+    Cam a, b;
+    DevBuf<double> Ps[2], rec[2], partA[2], tot, partC, delta, trace;
+    DevBuf<StereoState> st;
+    int* done_host = nullptr;     // pinned: the decide / rig kernels set it when the loop is over
+    int64_t M = 0;
+    int nwg = 0, model_a = 0, model_b = 0;
+    StereoBufs bufs{};
+    ~StereoRun() { if (done_host) (void)hipHostFree(done_host); }
+
+    static int upload_cam(Cam& c, int model, int64_t M, const int64_t* offs, const double* uv, const double* xyz,
+                          const double* shared) {
+        const int64_t n = offs[M];
+        const size_t L = 5 + (size_t)num_distortion(model);
+        HIP_TRY(c.offs.alloc((size_t)M + 1));
+        HIP_TRY(c.uv.alloc((size_t)std::max<int64_t>(n, 1)));
+        HIP_TRY(c.xyz.alloc((size_t)std::max<int64_t>(n, 1) * 3));
+        HIP_TRY(c.shared.alloc(L));
+        HIP_TRY(hipMemcpy(c.offs.p, offs, ((size_t)M + 1) * 8, hipMemcpyHostToDevice));
+        if (n) HIP_TRY(hipMemcpy(c.uv.p, uv, (size_t)n * 16, hipMemcpyHostToDevice));
+        if (n) HIP_TRY(hipMemcpy(c.xyz.p, xyz, (size_t)n * 24, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c.shared.p, shared, L * 8, hipMemcpyHostToDevice));
+        return CALIB_OK;
+    }
+
+    // the start point goes into buffer 0, which the bootstrap round evaluates as its candidate (cur = 1)
+    int begin(const calib_stereo_problem_t* p, const double* Ps0, int max_iters, double lam, double lam_min,
+              double lam_max, double err_min, bool want_trace, bool want_notify) {
+        M = p->num_views; model_a = p->model_a; model_b = p->model_b;
+        nwg = (int)((M + 15) / 16);
+        const size_t K = 6 + 6 * (size_t)M;
+        int rc = upload_cam(a, p->model_a, M, p->offs_a, p->uv_a, p->xyz_a, p->shared_a);
+        if (rc) return rc;
+        rc = upload_cam(b, p->model_b, M, p->offs_b, p->uv_b, p->xyz_b, p->shared_b);
+        if (rc) return rc;
+        for (int s = 0; s < 2; ++s) {
+            HIP_TRY(Ps[s].alloc(K));
+            HIP_TRY(rec[s].alloc((size_t)M * kStRecord));
+            HIP_TRY(partA[s].alloc((size_t)nwg * kStTot));
+        }
+        HIP_TRY(tot.alloc(2 * kStTot));
+        HIP_TRY(partC.alloc((size_t)nwg * kStSchur));
+        HIP_TRY(delta.alloc(K));
+        HIP_TRY(st.alloc(1));
+        HIP_TRY(hipMemcpy(Ps[0].p, Ps0, K * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(Ps[1].p, Ps0, K * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(tot.p, 0, 2 * kStTot * 8));
+        if (want_trace) {
+            HIP_TRY(trace.alloc((size_t)max_iters * kStTrace));
+            HIP_TRY(hipMemset(trace.p, 0, (size_t)max_iters * kStTrace * 8));
+        }
+        StereoState s{};
+        s.lam = lam; s.lam_min = lam_min; s.lam_max = lam_max; s.err_min = err_min;
+        s.err_cur = s.last_err = std::nan("");
+        s.cur = 1; s.max_iters = max_iters;
+        if (want_notify) {
+            void* hp = nullptr; void* dp = nullptr;
+            if (hipHostMalloc(&hp, sizeof(int), hipHostMallocMapped) == hipSuccess) {
+                done_host = static_cast<int*>(hp);
+                *done_host = 0;
+                if (hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) s.notify = static_cast<int*>(dp);
+            }
+            (void)hipGetLastError();
+        }
+        HIP_TRY(hipMemcpy(st.p, &s, sizeof s, hipMemcpyHostToDevice));
+        bufs = StereoBufs{{Ps[0].p, Ps[1].p}, {rec[0].p, rec[1].p}, {partA[0].p, partA[1].p}, {tot.p, tot.p + kStTot},
+                          partC.p, delta.p, trace.p, st.p, M};
+        return CALIB_OK;
+    }
+
+    // blocks at the candidate, then its totals and the decision
+    int evaluate() {
+        const StereoCam ca = a.view(), cb = b.view();
+        const StereoBufs bf = bufs;
+        const unsigned grid = (unsigned)nwg;
+        const int rc = dispatch_model(model_a, [&](auto fa) -> int {
+            return dispatch_model(model_b, [&](auto fb) -> int {
+                hipLaunchKernelGGL((stereo_blocks_kernel<decltype(fa)::MODEL, decltype(fb)::MODEL>), dim3(grid), dim3(256),
+                                   0, 0, ca, cb, bf);
+                LAUNCHED(kNoHandle, "stereo_blocks_kernel");
+                return CALIB_OK;
+            });
+        });
+        if (rc) return rc;
+        hipLaunchKernelGGL(stereo_decide_kernel<kStTot>, dim3(1), dim3(256), 0, 0, bf, nwg);
+        LAUNCHED(kNoHandle, "stereo_decide_kernel");
+        return CALIB_OK;
+    }
+
+    // the step at the accepted point: Schur complement, rig solve, back-substitution into the next candidate
+    int step() {
+        const StereoBufs bf = bufs;
+        hipLaunchKernelGGL(stereo_schur_kernel<16>, dim3((unsigned)nwg), dim3(256), 0, 0, a.view(), b.view(), bf);
+        LAUNCHED(kNoHandle, "stereo_schur_kernel");
+        hipLaunchKernelGGL(stereo_rig_kernel<kStSchur>, dim3(1), dim3(256), 0, 0, bf, nwg);
+        LAUNCHED(kNoHandle, "stereo_rig_kernel");
+        hipLaunchKernelGGL(stereo_backsub_kernel<64>, dim3((unsigned)((M + 63) / 64)), dim3(64), 0, 0, bf);
+        LAUNCHED(kNoHandle, "stereo_backsub_kernel");
+        return CALIB_OK;
+    }
+
+    int state(StereoState& s) {
+        HIP_TRY(hipMemcpy(&s, st.p, sizeof s, hipMemcpyDeviceToHost));
+        return CALIB_OK;
+    }
+};
+
+int stereo_singular() {
+    return fail(CALIB_E_SINGULAR, "stereo normal equations singular: a view with fewer than three points in total or a "
+                                  "pivot that is not positive, or a rig that no view with points in camera b constrains");
+}
+
+}  // namespace
+
+extern "C" {
+
+int calib_stereo_normal_eq(const calib_stereo_problem_t* problem, const double* Ps, double* out_B, double* out_E,
+                           double* out_V, double* out_g, double* out_sse_ab, int device_id) {
+    int rc = check_stereo(problem, Ps);
+    if (rc) return rc;
+    rc = use_device(device_id);
+    if (rc) return rc;
+    StereoRun run;
+    rc = run.begin(problem, Ps, 1, 0.0, 0.0, 0.0, 0.0, false, false);
+    if (rc) return rc;
+    rc = run.evaluate();
+    if (rc) return rc;
+    const size_t M = (size_t)problem->num_views;
+    std::vector<double> rec(M * kStRecord), tot(kStTot);
+    HIP_TRY(hipMemcpy(rec.data(), run.rec[0].p, rec.size() * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(tot.data(), run.tot.p, kStTot * 8, hipMemcpyDeviceToHost));
+    auto sym = [](const double* t, double* o) {
+        for (int r = 0; r < 6; ++r)
+            for (int c = 0; c <= r; ++c) o[r * 6 + c] = o[c * 6 + r] = t[r * (r + 1) / 2 + c];
+    };
+    if (out_B) sym(tot.data(), out_B);
+    if (out_g) std::copy(tot.begin() + 21, tot.begin() + 27, out_g);
+    if (out_sse_ab) { out_sse_ab[0] = tot[27]; out_sse_ab[1] = tot[28]; }
+    for (size_t v = 0; v < M; ++v) {
+        const double* r = rec.data() + v * kStRecord;
+        if (out_V) sym(r + kStV, out_V + v * 36);
+        if (out_E) std::copy(r + kStE, r + kStE + 36, out_E + v * 36);
+        if (out_g) std::copy(r + kStGv, r + kStGv + 6, out_g + 6 + v * 6);
+    }
+    return CALIB_OK;
+}
+
+int calib_stereo_step_delta(const calib_stereo_problem_t* problem, const double* Ps, double lambda, double* out_delta,
+                            int device_id) {
+    int rc = check_stereo(problem, Ps);
+    if (rc) return rc;
+    rc = use_device(device_id);
+    if (rc) return rc;
+    StereoRun run;
+    rc = run.begin(problem, Ps, 1, lambda, 0.0, 0.0, 0.0, false, false);
+    if (rc) return rc;
+    rc = run.evaluate();
+    if (rc) return rc;
+    rc = run.step();
+    if (rc) return rc;
+    StereoState s;
+    rc = run.state(s);
+    if (rc) return rc;
+    if (s.error) return stereo_singular();
+    if (out_delta) HIP_TRY(hipMemcpy(out_delta, run.delta.p, (6 + 6 * (size_t)problem->num_views) * 8, hipMemcpyDeviceToHost));
+    return CALIB_OK;
+}
+
+int calib_refine_stereo(const calib_stereo_problem_t* problem, double* Ps_inout, int max_iters, double lam_init,
+                        double lam_min, double lam_max, double err_min, double* out_sse, double* out_sse_ab,
+                        int* out_iters, double* out_trace, int device_id) {
+    if (max_iters <= 0) return fail(CALIB_E_INVALID, "max_iters must be >= 1");
+    int rc = check_stereo(problem, Ps_inout);
+    if (rc) return rc;
+    rc = use_device(device_id);
+    if (rc) return rc;
+    StereoRun run;
+    rc = run.begin(problem, Ps_inout, max_iters, lam_init, lam_min, lam_max, err_min, out_trace != nullptr, true);
+    if (rc) return rc;
+    // round 0 evaluates the start point; round r >= 1 decides iteration r - 1. The host runs ahead of the device: the
+    // done word in pinned memory stops the enqueueing (rounds already in the queue return at once); without such a word,
+    // a synchronised look at the state every 8 rounds.
+    StereoState s;
+    for (int r = 0; r <= max_iters; ++r) {
+        rc = run.evaluate();
+        if (rc) return rc;
+        rc = run.step();
+        if (rc) return rc;
+        if (run.done_host) {
+            if (*static_cast<volatile int*>(run.done_host)) break;
+        } else if ((r + 1) % 8 == 0) {
+            rc = run.state(s);
+            if (rc) return rc;
+            if (s.done) break;
+        }
+    }
+    rc = run.state(s);
+    if (rc) return rc;
+    if (s.error) return stereo_singular();
+    const size_t K = 6 + 6 * (size_t)problem->num_views;
+    HIP_TRY(hipMemcpy(Ps_inout, run.Ps[s.cur].p, K * 8, hipMemcpyDeviceToHost));
+    if (out_sse) *out_sse = s.last_err;
+    if (out_iters) *out_iters = s.iters;
+    if (out_sse_ab) HIP_TRY(hipMemcpy(out_sse_ab, run.tot.p + s.cur * kStTot + 27, 16, hipMemcpyDeviceToHost));
+    if (out_trace && s.iters > 0)
+        HIP_TRY(hipMemcpy(out_trace, run.trace.p, (size_t)s.iters * kStTrace * 8, hipMemcpyDeviceToHost));
+    return CALIB_OK;
 }
 
 }  // extern "C"

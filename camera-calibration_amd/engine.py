@@ -765,3 +765,68 @@ def remap(image, mapx, mapy, border=0.0, device=0):
                                             image.shape[2], nat.f32ptr(mapx), nat.f32ptr(mapy), h, w, float(border),
                                             out.ctypes.data_as(ctypes.c_void_p), int(device)))
     return out
+
+
+# ---- stereo calibration with both cameras known (calib_stereo_*, csrc/stereo.hpp) -----------------------------------
+def _stereoProblem(cameraA, cameraB):
+    """camera = (modelId, shared (L,), viewOffsets (M+1,), sensorPoints (n,2), modelPoints (n,3)) -> (the C struct, the
+    arrays it points into: keep them alive for the call)"""
+    keep, fields = [], {}
+    M = None
+    for tag, (modelId, shared, offs, s, m) in (("a", cameraA), ("b", cameraB)):
+        if modelId not in NUM_SHARED:
+            raise ValueError(f"camera {tag}: unknown distortion model id {modelId!r}")
+        shared = np.ascontiguousarray(np.asarray(shared, dtype=np.float64).ravel())
+        if shared.shape[0] != NUM_SHARED[modelId]:
+            raise ValueError(f"camera {tag}: expected {NUM_SHARED[modelId]} shared parameters, got {shared.shape[0]}")
+        offs, s, m = _packedViews(viewOffsets=offs, sensorPoints=s, modelPoints=m)
+        if M is not None and offs.shape[0] - 1 != M:
+            raise ValueError(f"the cameras have {M} and {offs.shape[0] - 1} views")
+        M = offs.shape[0] - 1
+        keep += [shared, offs, s, m]
+        fields.update({f"model_{tag}": modelId, f"offs_{tag}": nat.i64ptr(offs), f"uv_{tag}": nat.dptr(s),
+                       f"xyz_{tag}": nat.dptr(m), f"shared_{tag}": nat.dptr(shared)})
+    return nat.StereoProblem(num_views=M, **fields), keep, M
+
+
+def _stereoPs(Ps, M):
+    Ps = np.ascontiguousarray(np.asarray(Ps, dtype=np.float64).ravel())
+    if Ps.shape[0] != 6 + 6 * M:
+        raise ValueError(f"Expected shape ({6 + 6 * M},) = (rig, {M} poses), got {Ps.shape}")
+    return Ps
+
+
+def stereoNormalEquations(cameraA, cameraB, Ps, device=0):
+    """Block-arrow normal equations of the stereo problem at Ps = (rig, pose_0, ..) -> dict B (6,6), E (M,6,6) [rig row,
+    view column], V (M,6,6), g (6 + 6 M,), sseA, sseB. Cameras as _stereoProblem takes them."""
+    prob, keep, M = _stereoProblem(cameraA, cameraB)
+    Ps = _stereoPs(Ps, M)
+    B, E, V, g, ab = np.empty((6, 6)), np.empty((M, 6, 6)), np.empty((M, 6, 6)), np.empty(6 + 6 * M), np.empty(2)
+    nat.check(nat.loadLibrary().calib_stereo_normal_eq(ctypes.byref(prob), nat.dptr(Ps), nat.dptr(B), nat.dptr(E),
+                                                       nat.dptr(V), nat.dptr(g), nat.dptr(ab), int(device)))
+    return {"B": B, "E": E, "V": V, "g": g, "sseA": float(ab[0]), "sseB": float(ab[1])}
+
+
+def stereoStepDelta(cameraA, cameraB, Ps, lam, device=0):
+    """delta (6 + 6 M,) = (J^T J + lam diag J^T J)^-1 J^T r of the stereo problem at Ps, solved on the device."""
+    prob, keep, M = _stereoProblem(cameraA, cameraB)
+    Ps = _stereoPs(Ps, M)
+    delta = np.empty(6 + 6 * M)
+    nat.check(nat.loadLibrary().calib_stereo_step_delta(ctypes.byref(prob), nat.dptr(Ps), float(lam), nat.dptr(delta),
+                                                        int(device)))
+    return delta
+
+
+def refineStereo(cameraA, cameraB, Ps0, maxIters, lamInit=LAMBDA_INITIAL, lamMin=LAMBDA_MIN, lamMax=LAMBDA_MAX,
+                 errMin=PT_ERROR_MIN, device=0):
+    """The LM loop on Ps = (rig, pose_0, ..) with both cameras held fixed -> (sse [pre-update, as the reference
+    returns], Ps, iters, trace (iters, 5 + 6), (sseA, sseB) at the returned Ps)."""
+    prob, keep, M = _stereoProblem(cameraA, cameraB)
+    Ps = _stereoPs(Ps0, M).copy()
+    maxIters = int(maxIters)
+    sse, iters, ab = ctypes.c_double(0.0), ctypes.c_int(0), np.empty(2)
+    trace = np.zeros((max(maxIters, 1), nat.TRACE_HEADER + 6))
+    nat.check(nat.loadLibrary().calib_refine_stereo(
+        ctypes.byref(prob), nat.dptr(Ps), maxIters, float(lamInit), float(lamMin), float(lamMax), float(errMin),
+        ctypes.byref(sse), nat.dptr(ab), ctypes.byref(iters), nat.dptr(trace), int(device)))
+    return sse.value, Ps, iters.value, trace[:iters.value], (float(ab[0]), float(ab[1]))

@@ -373,6 +373,41 @@ int calib_distortion_normal_equations(int model, int64_t num_views, const int64_
 int calib_profile_enable(calib_handle_t h, int on);
 int calib_profile_read(calib_handle_t h, int which, double* out_total_ms, int64_t* out_launches);
 
+/* ---- stereo calibration with both cameras KNOWN: the rig between two calibrated cameras --------------------------
+ * Cameras a and b, each radtan or fisheye with its shared vector (alpha beta gamma uc vc k.., the order of P) held
+ * fixed, see M views of one board; each camera's correspondences are a CSR of their own (the cameras may see
+ * different corners, either side of a view may be empty). Unknowns Ps (6 + 6 M) = (rig, pose_0, .., pose_{M-1}), every
+ * 6-tuple rho_x, rho_y, rho_z [DEGREES], t as the view blocks of P: pose_i takes board points into camera a's frame,
+ * Xa = R_i X + t_i; the rig takes camera a's frame into camera b's, Xb = R_rig Xa + t_rig. Residuals
+ * uv_a - project_a(Xa) and uv_b - project_b(Xb); the error is the sum of their squared norms over both cameras.
+ * Stateless: host pointers in and out, no handle. Any output may be NULL. Every sum is fixed-order: a call is bitwise
+ * reproducible. A bad model id, num_views < 1, max_iters <= 0, a NULL input or an offset array that does not start at 0
+ * or decreases is CALIB_E_INVALID before any device call.
+ *
+ * calib_stereo_normal_eq: the block-arrow normal equations at Ps -- out_B (6,6) rig block, out_E (M,6,6) rig row x view
+ *   column, out_V (M,6,6), out_g (6 + 6 M) = J^T r in the order of Ps, out_sse_ab (2) the error per camera.
+ * calib_stereo_step_delta: delta = (J^T J + lambda diag J^T J)^-1 J^T r at Ps through the Schur complement of the view
+ *   blocks. CALIB_E_SINGULAR when a view has fewer than three points in total or a pivot of V_i + lambda diag V_i that
+ *   is not positive (an empty view), or when the rig's Schur complement has such a pivot (no view with points in b).
+ * calib_refine_stereo: the loop of src/calibrate.py:143-171 on Ps with the rules of calib_refine. out_sse = err(Ps)
+ *   before the last update; out_sse_ab (2) = the error per camera AT the returned Ps; out_trace rows are
+ *   CALIB_TRACE_HEADER + 6 doubles, the six rig parameters before the update in the place of the shared ones.
+ *   On CALIB_E_SINGULAR Ps_inout is left as it was. */
+typedef struct {
+    int model_a, model_b;
+    int64_t num_views;
+    const int64_t* offs_a; const double *uv_a, *xyz_a, *shared_a;
+    const int64_t* offs_b; const double *uv_b, *xyz_b, *shared_b;
+} calib_stereo_problem_t;
+
+int calib_stereo_normal_eq(const calib_stereo_problem_t* problem, const double* Ps, double* out_B, double* out_E,
+                           double* out_V, double* out_g, double* out_sse_ab, int device_id);
+int calib_stereo_step_delta(const calib_stereo_problem_t* problem, const double* Ps, double lambda, double* out_delta,
+                            int device_id);
+int calib_refine_stereo(const calib_stereo_problem_t* problem, double* Ps_inout, int max_iters, double lam_init,
+                        double lam_min, double lam_max, double err_min, double* out_sse, double* out_sse_ab,
+                        int* out_iters, double* out_trace, int device_id);
+
 #ifdef __cplusplus
 }
 #endif
