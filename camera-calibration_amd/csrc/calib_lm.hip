@@ -4,6 +4,7 @@
 #include "kernels.hpp"
 #include "undistort.hpp"
 #include "stereo.hpp"
+#include "rectify.hpp"
 #include "host_rows.hpp"
 #include "launch_plan.hpp"
 #include "shard_layout.hpp"
@@ -874,7 +875,7 @@ bool shared_covariance(const double* red, int L, uint32_t fixed_mask, double sig
 // ============================================================================ C-ABI
 extern "C" {
 
-int calib_version(void) { return 440; }   // 4.4: calib_stereo_normal_eq, calib_stereo_step_delta, calib_refine_stereo
+int calib_version(void) { return 450; }   // 4.5: calib_rectify_maps, calib_rectify_points, calib_triangulate
 
 const char* calib_last_error(void) { return g_err.c_str(); }
 
@@ -2287,6 +2288,156 @@ int calib_refine_stereo(const calib_stereo_problem_t* problem, double* Ps_inout,
     if (out_sse_ab) HIP_TRY(hipMemcpy(out_sse_ab, run.tot.p + s.cur * kStTot + 27, 16, hipMemcpyDeviceToHost));
     if (out_trace && s.iters > 0)
         HIP_TRY(hipMemcpy(out_trace, run.trace.p, (size_t)s.iters * kStTrace * 8, hipMemcpyDeviceToHost));
+    return CALIB_OK;
+}
+
+}  // extern "C"
+
+// ---- using a calibrated rig (rectify.hpp): rectify maps, rectified points, triangulation -------------------------
+namespace {
+
+// a (3,3) row-major rotation, NULL = identity; false unless |det R - 1| <= 1e-6
+bool rotation_of(const double* R, double (&m)[9]) {
+    static const double I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    for (int j = 0; j < 9; ++j) m[j] = R ? R[j] : I[j];
+    const double det = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) +
+                       m[2] * (m[3] * m[7] - m[4] * m[6]);
+    return std::fabs(det - 1.0) <= 1e-6;                    // false for NaN
+}
+
+// One camera's side of calib_triangulate: the pixels and the ideal normalised points undistort_points_kernel finds for
+// them, all on the device.
+struct TriSide {
+    DevBuf<double2> uv, xd, xy;
+    DevBuf<double> k;
+    DevBuf<int32_t> status;
+
+    int run(int model, const Pinhole& cam, const double* kHost, int64_t n, const double* uvHost) {
+        const int nk = num_distortion(model);
+        std::vector<double> norm((size_t)n * 2);            // pixels -> distorted normalised points
+        for (int64_t i = 0; i < n; ++i) {
+            const double yd = (uvHost[2 * i + 1] - cam.vc) / cam.be;
+            norm[2 * i] = (uvHost[2 * i] - cam.uc - cam.ga * yd) / cam.al;
+            norm[2 * i + 1] = yd;
+        }
+        HIP_TRY(uv.alloc((size_t)n)); HIP_TRY(xd.alloc((size_t)n)); HIP_TRY(xy.alloc((size_t)n));
+        HIP_TRY(k.alloc(nk)); HIP_TRY(status.alloc((size_t)n));
+        HIP_TRY(hipMemcpy(uv.p, uvHost, (size_t)n * 16, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(xd.p, norm.data(), (size_t)n * 16, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(k.p, kHost, (size_t)nk * 8, hipMemcpyHostToDevice));
+        const unsigned blocks = (unsigned)((n + 255) / 256);
+        return dispatch_model(model, [&](auto form) -> int {
+            hipLaunchKernelGGL((undistort_points_kernel<decltype(form)::MODEL>), dim3(blocks), dim3(256), 0, 0,
+                               (const double2*)xd.p, (const double*)k.p, n, xy.p, status.p);
+            LAUNCHED(kNoHandle, "undistort_points_kernel");
+            return CALIB_OK;
+        });
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int calib_rectify_maps(int model, const double* A, const double* k, const double* R, const double* P, int width,
+                       int height, float* out_mapx, float* out_mapy, int device_id) {
+    if (!A || !k || !P || !out_mapx || !out_mapy) return fail(CALIB_E_INVALID, "null argument");
+    if (!known_model(model)) return fail(CALIB_E_INVALID, "unknown distortion model");
+    if (width <= 0 || height <= 0) return fail(CALIB_E_INVALID, "width and height must be positive");
+    if ((int64_t)width * height > (int64_t)INT32_MAX) return fail(CALIB_E_INVALID, "a map has at most 2^31 - 1 pixels");
+    Pinhole cam, dst;
+    if (!pinhole_of(A, cam) || !pinhole_of(P, dst))
+        return fail(CALIB_E_INVALID, "alpha and beta of a camera matrix must not be 0");
+    Rot3 rot;
+    if (!rotation_of(R, rot.m)) return fail(CALIB_E_INVALID, "R is not a rotation (|det R - 1| > 1e-6)");
+    int rc = use_device(device_id);
+    if (rc) return rc;
+    const int nk = num_distortion(model);
+    const unsigned total = (unsigned)width * (unsigned)height;
+    DevBuf<double> dk;
+    DevBuf<float> dmaps;                                    // mapx, then mapy from the next 16-byte boundary
+    const size_t plane = ((size_t)total + 3) / 4 * 4;
+    HIP_TRY(dk.alloc(nk)); HIP_TRY(dmaps.alloc(2 * plane));
+    HIP_TRY(hipMemcpy(dk.p, k, (size_t)nk * 8, hipMemcpyHostToDevice));
+    const unsigned perBlock = 256u * (unsigned)kMapCols;
+    const unsigned blocks = (unsigned)(((uint64_t)total + perBlock - 1) / perBlock);
+    rc = dispatch_model(model, [&](auto form) -> int {
+        hipLaunchKernelGGL((rectify_map_kernel<decltype(form)::MODEL>), dim3(blocks), dim3(256), 0, 0, cam, dst, rot,
+                           (const double*)dk.p, (unsigned)width, total, dmaps.p, dmaps.p + plane);
+        LAUNCHED(kNoHandle, "rectify_map_kernel");
+        return CALIB_OK;
+    });
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(out_mapx, dmaps.p, (size_t)total * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_mapy, dmaps.p + plane, (size_t)total * 4, hipMemcpyDeviceToHost));
+    return CALIB_OK;
+}
+
+int calib_rectify_points(int model, int64_t n, const double* A, const double* k, const double* uv, const double* R,
+                         const double* P, double* out_uv, int32_t* out_status, int device_id) {
+    if (n < 0 || (n > 0 && (!uv || !out_uv)) || !k || !A || !P) return fail(CALIB_E_INVALID, "null argument");
+    if (!known_model(model)) return fail(CALIB_E_INVALID, "unknown distortion model");
+    Pinhole cam, dst;
+    if (!pinhole_of(A, cam) || !pinhole_of(P, dst))
+        return fail(CALIB_E_INVALID, "alpha and beta of a camera matrix must not be 0");
+    double m[9];
+    if (!rotation_of(R, m)) return fail(CALIB_E_INVALID, "R is not a rotation (|det R - 1| > 1e-6)");
+    if (n == 0) return CALIB_OK;
+    std::vector<int32_t> status((size_t)n);
+    const int rc = calib_undistort_points(model, n, A, k, uv, nullptr, out_uv, status.data(), device_id);
+    if (rc) return rc;
+    const double nan = std::nan("");
+    for (int64_t i = 0; i < n; ++i) {                       // ideal normalised points -> the rotated frame -> pixels of P
+        const double x = out_uv[2 * i], y = out_uv[2 * i + 1];
+        const double X = m[0] * x + m[1] * y + m[2], Y = m[3] * x + m[4] * y + m[5], Z = m[6] * x + m[7] * y + m[8];
+        const bool ok = status[(size_t)i] == 0 && Z > 0.0;
+        const double px = X / Z, py = Y / Z;
+        out_uv[2 * i] = ok ? dst.al * px + dst.ga * py + dst.uc : nan;
+        out_uv[2 * i + 1] = ok ? dst.be * py + dst.vc : nan;
+        status[(size_t)i] = ok ? 0 : 1;
+    }
+    if (out_status) std::copy(status.begin(), status.end(), out_status);
+    return CALIB_OK;
+}
+
+int calib_triangulate(int model_a, const double* Aa, const double* ka, int model_b, const double* Ab, const double* kb,
+                      const double* R, const double* t, int64_t n, const double* uv_a, const double* uv_b, double* out_X,
+                      double* out_sse, int32_t* out_status, int device_id) {
+    if (n < 0 || (n > 0 && (!uv_a || !uv_b || !out_X)) || !Aa || !ka || !Ab || !kb || !R || !t)
+        return fail(CALIB_E_INVALID, "null argument");
+    if (!known_model(model_a) || !known_model(model_b)) return fail(CALIB_E_INVALID, "unknown distortion model");
+    Pinhole ca, cb;
+    if (!pinhole_of(Aa, ca) || !pinhole_of(Ab, cb))
+        return fail(CALIB_E_INVALID, "alpha and beta of a camera matrix must not be 0");
+    Rigid rig;
+    if (!rotation_of(R, rig.R)) return fail(CALIB_E_INVALID, "R is not a rotation (|det R - 1| > 1e-6)");
+    for (int j = 0; j < 3; ++j) rig.t[j] = t[j];
+    if (n == 0) return CALIB_OK;
+    int rc = use_device(device_id);
+    if (rc) return rc;
+    TriSide a, b;
+    rc = a.run(model_a, ca, ka, n, uv_a);
+    if (rc) return rc;
+    rc = b.run(model_b, cb, kb, n, uv_b);
+    if (rc) return rc;
+    DevBuf<double> dX, dsse;
+    DevBuf<int32_t> dstatus;
+    HIP_TRY(dX.alloc((size_t)n * 3)); HIP_TRY(dsse.alloc((size_t)n)); HIP_TRY(dstatus.alloc((size_t)n));
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    rc = dispatch_model(model_a, [&](auto fa) -> int {
+        return dispatch_model(model_b, [&](auto fb) -> int {
+            hipLaunchKernelGGL((triangulate_kernel<decltype(fa)::MODEL, decltype(fb)::MODEL>), dim3(blocks), dim3(256), 0, 0,
+                               ca, (const double*)a.k.p, cb, (const double*)b.k.p, rig, n, (const double2*)a.xy.p,
+                               (const int32_t*)a.status.p, (const double2*)b.xy.p, (const int32_t*)b.status.p,
+                               (const double2*)a.uv.p, (const double2*)b.uv.p, dX.p, dsse.p, dstatus.p);
+            LAUNCHED(kNoHandle, "triangulate_kernel");
+            return CALIB_OK;
+        });
+    });
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(out_X, dX.p, (size_t)n * 24, hipMemcpyDeviceToHost));
+    if (out_sse) HIP_TRY(hipMemcpy(out_sse, dsse.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (out_status) HIP_TRY(hipMemcpy(out_status, dstatus.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     return CALIB_OK;
 }
 

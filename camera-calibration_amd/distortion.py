@@ -64,6 +64,24 @@ class DistortionModel:
             raise ValueError(f"size: expected (width, height), got {size!r}") from None
         return engine.undistortMaps(self.modelId, A, self._checkK(k), width, height, newA)
 
+    def rectifyMaps(self, A, k, R, P, size):
+        """undistortMaps with a rotation: size = (width, height) of the rectified image, R (3,3) or None the rotation
+        from the camera's frame into the rectified one, P its camera matrix ((3,3), or the (3,4) projection matrix of
+        stereoRectify) -> (mapx, mapy), float32 (height, width); NaN where the pixel's ray does not enter the camera's
+        front half space (remap turns that into the border value)."""
+        try:
+            width, height = size
+        except (TypeError, ValueError):
+            raise ValueError(f"size: expected (width, height), got {size!r}") from None
+        return engine.rectifyMaps(self.modelId, A, self._checkK(k), R, P, width, height)
+
+    def rectifyPoints(self, A, k, uv, R, P, returnStatus=False):
+        """uv (N,2) pixels of the distorted image -> (N,2) pixels of the rectified one (R, P as in rectifyMaps). A row
+        is NaN where the model has no inverse or the point lies behind the rectified camera; returnStatus=True also
+        returns the (N,) int32 status, 0 = ok, 1 = not."""
+        out, status = engine.rectifyPoints(self.modelId, A, self._checkK(k), uv, R, P)
+        return (out, status) if returnStatus else out
+
     def estimateDistortion(self, A, allDetections, allBoardPosesInCamera, device=0):
         """Linear least-squares start value of k given A and the board poses (src/distortion.py:70,
         110-191 radial-tangential, 222-271 fisheye): D^T D and D^T Ddot are formed on the device

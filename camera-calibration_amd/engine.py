@@ -830,3 +830,82 @@ def refineStereo(cameraA, cameraB, Ps0, maxIters, lamInit=LAMBDA_INITIAL, lamMin
         ctypes.byref(prob), nat.dptr(Ps), maxIters, float(lamInit), float(lamMin), float(lamMax), float(errMin),
         ctypes.byref(sse), nat.dptr(ab), ctypes.byref(iters), nat.dptr(trace), int(device)))
     return sse.value, Ps, iters.value, trace[:iters.value], (float(ab[0]), float(ab[1]))
+
+
+# ---- using a calibrated rig (calib_rectify_*, calib_triangulate, csrc/rectify.hpp): arguments are checked first --------
+def _rotation(R, name="R"):
+    if R is None:
+        return None
+    R = np.ascontiguousarray(R, dtype=np.float64)
+    if R.shape != (3, 3):
+        raise ValueError(f"{name}: expected shape (3, 3), got {R.shape}")
+    if not abs(np.linalg.det(R) - 1.0) <= 1e-6:
+        raise ValueError(f"{name}: not a rotation (det = {np.linalg.det(R)!r})")
+    return R
+
+
+def _destinationMatrix(P):
+    """the (3,3) camera matrix of a rectified image: P itself, or the left block of a (3,4) projection matrix"""
+    P = np.asarray(P, dtype=np.float64)
+    if P.shape not in ((3, 3), (3, 4)):
+        raise ValueError(f"P: expected shape (3, 3) or (3, 4), got {P.shape}")
+    return np.ascontiguousarray(P[:, :3])
+
+
+def rectifyMaps(modelId, A, k, R, P, width, height, device=0):
+    """(mapx, mapy), float32 (height, width): where pixel (row, col) of the rectified image (rotation R or None, camera
+    matrix P) lies in the distorted one; NaN where its ray does not enter the camera's front half space."""
+    width, height = int(width), int(height)
+    if width <= 0 or height <= 0:
+        raise ValueError(f"size: width and height must be positive, got ({width}, {height})")
+    A, k, R, P = _cameraMatrix(A, "A"), _coefficients(modelId, k), _rotation(R), _destinationMatrix(P)
+    mapx = np.empty((height, width), dtype=np.float32)
+    mapy = np.empty((height, width), dtype=np.float32)
+    nat.requireDevice()
+    nat.check(nat.loadLibrary().calib_rectify_maps(modelId, nat.dptr(A), nat.dptr(k), nat.dptr(R), nat.dptr(P), width,
+                                                   height, nat.f32ptr(mapx), nat.f32ptr(mapy), int(device)))
+    return mapx, mapy
+
+
+def _pixels(uv, name):
+    uv = np.asarray(uv, dtype=np.float64)
+    if uv.ndim != 2 or uv.shape[1] != 2:
+        raise ValueError(f"{name}: expected shape (None, 2), got {uv.shape}")
+    return np.ascontiguousarray(uv)
+
+
+def rectifyPoints(modelId, A, k, uv, R, P, device=0):
+    """uv (N,2) pixels of the distorted image -> (uv (N,2) pixels of the rectified one, status (N,) int32: 0, or 1 with
+    the row NaN where the model has no inverse or the rotated point lies behind the rectified camera)."""
+    uv = _pixels(uv, "uv")
+    A, k, R, P = _cameraMatrix(A, "A"), _coefficients(modelId, k), _rotation(R), _destinationMatrix(P)
+    out = np.empty_like(uv)
+    status = np.empty(uv.shape[0], dtype=np.int32)
+    nat.requireDevice()
+    nat.check(nat.loadLibrary().calib_rectify_points(
+        modelId, uv.shape[0], nat.dptr(A), nat.dptr(k), nat.dptr(uv), nat.dptr(R), nat.dptr(P), nat.dptr(out),
+        status.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(device)))
+    return out, status
+
+
+def triangulate(modelIdA, Aa, ka, modelIdB, Ab, kb, R, t, uvA, uvB, device=0):
+    """Matched pixels uvA, uvB (N,2) of two cameras joined by Xb = R Xa + t -> (X (N,3) in camera a's frame, sse (N,) the
+    four pixel residuals squared and summed at X, status (N,) int32: 0 ok, 1 no inverse, 2 degenerate geometry, 3 not
+    converged; X and sse are NaN where it is not 0)."""
+    uvA, uvB = _pixels(uvA, "uvA"), _pixels(uvB, "uvB")
+    if uvA.shape != uvB.shape:
+        raise ValueError(f"uvA and uvB: expected one shape, got {uvA.shape} and {uvB.shape}")
+    Aa, ka = _cameraMatrix(Aa, "A of camera a"), _coefficients(modelIdA, ka)
+    Ab, kb = _cameraMatrix(Ab, "A of camera b"), _coefficients(modelIdB, kb)
+    R = _rotation(np.eye(3) if R is None else R)
+    t = np.ascontiguousarray(t, dtype=np.float64).ravel()
+    if t.shape[0] != 3:
+        raise ValueError(f"t: expected 3 values, got {t.shape[0]}")
+    n = uvA.shape[0]
+    X, sse, status = np.empty((n, 3)), np.empty(n), np.empty(n, dtype=np.int32)
+    nat.requireDevice()
+    nat.check(nat.loadLibrary().calib_triangulate(
+        modelIdA, nat.dptr(Aa), nat.dptr(ka), modelIdB, nat.dptr(Ab), nat.dptr(kb), nat.dptr(R), nat.dptr(t), n,
+        nat.dptr(uvA), nat.dptr(uvB), nat.dptr(X), nat.dptr(sse),
+        status.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(device)))
+    return X, sse, status

@@ -125,6 +125,23 @@ class StereoCalibration:
         return rigCovarianceFromBlocks(ne["B"], ne["E"], ne["V"], ne["sseA"] + ne["sseB"],
                                        self.numPointsA + self.numPointsB)
 
+    def cameras(self):
+        """(cameraA, cameraB), each (distortionType, A, k) as stereoCalibrate took it"""
+        names = {v: n for n, v in engine.MODEL_IDS.items()}
+        return tuple((names[modelId], np.array([[s[0], s[2], s[3]], [0.0, s[1], s[4]], [0.0, 0.0, 1.0]]), s[5:].copy())
+                     for modelId, s in ((c[0], np.asarray(c[1], dtype=np.float64)) for c in self._problem))
+
+    def rectify(self, size, **kw):
+        """rectify.stereoRectify for this rig: size = (width, height) of the images -> StereoRectification"""
+        from . import rectify
+        kw.setdefault("device", self._device)
+        return rectify.stereoRectify(*self.cameras(), self.R, self.t, size, **kw)
+
+    def triangulate(self, uvA, uvB, returnStatus=False, returnError=False):
+        """rectify.triangulate for this rig: matched pixels (N,2) of the two cameras -> X (N,3) in camera a's frame"""
+        from . import rectify
+        return rectify.triangulate(*self.cameras(), self.R, self.t, uvA, uvB, returnStatus, returnError, self._device)
+
 
 def _solvedPoses(camera, views, maxIters, device):
     """estimatePoses on the views this camera can solve (at least 4 points) -> (W (M,4,4), ok (M,))"""

@@ -408,6 +408,46 @@ int calib_refine_stereo(const calib_stereo_problem_t* problem, double* Ps_inout,
                         double lam_min, double lam_max, double err_min, double* out_sse, double* out_sse_ab,
                         int* out_iters, double* out_trace, int device_id);
 
+/* ---- using a calibrated rig: rectify maps, rectified points, triangulation ---------------------------------------
+ * Stateless, host pointers, the work runs on device_id; cameras as in the undistortion entries (A (3,3) row-major, k the
+ * model's coefficients). R is a (3,3) row-major rotation; |det R - 1| > 1e-6 is CALIB_E_INVALID, as are a bad model id, a
+ * NULL input and alpha or beta equal to 0 in a camera matrix -- all before any device call.
+ *
+ * calib_rectify_maps: calib_undistort_maps with a rotation between the destination and the camera. R (NULL = identity)
+ *   takes the camera's frame into the rectified one, P is the (3,3) camera matrix of the destination (the left block of
+ *   a rectification's projection matrix). Destination pixel (col j, row i) looks along r = (x, y, 1),
+ *   y = (i - vc') / beta', x = (j - uc' - gamma' y) / alpha', that is along X = R^T r in the camera's own frame, and finds
+ *   it in the source at (mapx, mapy)(i, j) = A distort(X.x / X.z, X.y / X.z). A ray with X.z <= 0 (it does not enter the
+ *   camera's front half space) or a normalised point that is not finite gives NaN in BOTH planes, which calib_remap turns
+ *   into `border`. fp64, stored as fp32 rounded to nearest; width * height < 2^31. With R = NULL and P = A the maps equal
+ *   calib_undistort_maps' bit for bit.
+ * calib_rectify_points: uv (n,2) pixels of the distorted image -> out_uv (n,2) pixels of the rectified one: the inverse
+ *   of the model as calib_undistort_points finds it, then P (R (x, y, 1)) on the host. out_status (n) or NULL: 0, or 1
+ *   (out_uv NaN) where calib_undistort_points reports 1 or the rotated point has Z <= 0. n == 0 is CALIB_OK.
+ * calib_triangulate: the point X (camera a's frame) that the pixel pair uv_a[i], uv_b[i] sees, cameras a and b joined by
+ *   Xb = R Xa + t. Both pixels are inverted as calib_undistort_points does; the start is the midpoint of the common
+ *   perpendicular of the two rays; then at most 20 damped Gauss-Newton steps minimise the four PIXEL residuals
+ *   uv_a - project_a(X), uv_b - project_b(R X + t) through each camera's full forward model, with the damping rule of
+ *   calib_refine (lambda from 1e-3, / 10 on an accepted step, * 10 on a rejected one). A step is accepted when it lowers
+ *   the error; with eta = 2^-44 max(1, |uv|_inf) the trust in a projected pixel, a step whose predicted decrease is
+ *   below flat = eta (2 sqrt(error) + eta) -- less than two errors of rounded pixels can show -- is accepted unless the
+ *   error grows by more than flat. A point leaves the loop at a step <= 1e-14 |X|.
+ *   out_X (n,3); out_sse (n) or NULL: the four residuals squared and summed at X; out_status (n) or NULL, per pair:
+ *     0  ok
+ *     1  a pixel has no inverse in its camera (calib_undistort_points' status 1), or is not finite
+ *     2  degenerate geometry: the rays are parallel (sin^2 of their angle < 1e-12), or the start point or the end point
+ *        has Z <= 0 in either camera, or the damped 3 x 3 system has a pivot that is not positive
+ *     3  the last accepted step was still > 1e-9 |X|
+ *   out_X and out_sse are NaN wherever the status is not 0; the call itself still returns CALIB_OK. n == 0 is CALIB_OK.
+ *   One thread per pair, no atomics, no sums across threads: two calls agree bit for bit. */
+int calib_rectify_maps(int model, const double* A, const double* k, const double* R, const double* P, int width,
+                       int height, float* out_mapx, float* out_mapy, int device_id);
+int calib_rectify_points(int model, int64_t n, const double* A, const double* k, const double* uv, const double* R,
+                         const double* P, double* out_uv, int32_t* out_status, int device_id);
+int calib_triangulate(int model_a, const double* Aa, const double* ka, int model_b, const double* Ab, const double* kb,
+                      const double* R, const double* t, int64_t n, const double* uv_a, const double* uv_b, double* out_X,
+                      double* out_sse, int32_t* out_status, int device_id);
+
 #ifdef __cplusplus
 }
 #endif
