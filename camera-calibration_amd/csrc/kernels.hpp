@@ -1020,17 +1020,40 @@ __global__ __launch_bounds__(64 * kFusedWaves, kStreamMinBlocks) void fused_stre
         const int4* opsrc = reinterpret_cast<const int4*>(stream_ops) + 3 * lane;
         const int4 op0 = opsrc[0], op1 = opsrc[1], op2 = opsrc[2];
         const double pboth = request_shared_both<L>(P0, P1, sel, lane);      // both P buffers' shared parameters
-        int pn = p0 + sl < p1 ? p0 + sl : p1 - 1;
-        T2 m_n = uv[pn], xy_n = XY[pn];
-        T z_n = Z[pn];
+        // A batch's points: the wave's uniform bases (they advance one batch at a time, scalar work) plus the lane's
+        // constant 32-bit byte offset -- the lane's point of the batch, 16 bytes each in uv and XY, 8 in Z. Lanes past
+        // the share's last point follow that point; that can bind in the share's last batch only (pointOffsets).
+        const char* uvB = reinterpret_cast<const char*>(uv + p0);
+        const char* xyB = reinterpret_cast<const char*>(XY + p0);
+        const char* zB = reinterpret_cast<const char*>(Z + p0);
+        const unsigned sl16 = (unsigned)sl * 16u, sl8 = (unsigned)sl * 8u;
+        auto pointOffsets = [&](int q0, unsigned& o16, unsigned& o8) {
+            const int last = p1 - 1 - q0;                         // >= 0: the batch has a point
+            const unsigned lim = (unsigned)(last < 63 ? last : 63);  // (scalar)
+            o16 = sl16 < lim * 16u ? sl16 : lim * 16u;
+            o8 = sl8 < lim * 8u ? sl8 : lim * 8u;
+        };
+        unsigned off16, off8;
+        pointOffsets(p0, off16, off8);
+        auto loadUV = [&]() { return *reinterpret_cast<const T2*>(uvB + off16); };
+        auto loadXY = [&]() { return *reinterpret_cast<const T2*>(xyB + off16); };
+        auto loadZ = [&]() { return *reinterpret_cast<const T*>(zB + off8); };
+        // m, xy, z and vcx are the CURRENT batch's; the next batch's are requested into the same registers behind their
+        // last read (the residual), two contraction passes ahead of their first use
+        T2 xy = loadXY();
+        T z = loadZ();
+        T2 m = loadUV();
         // does the batch at q0 hold points of two views (boundary ve strictly inside its live points)?
         auto straddles = [&](int q0, int ve) { return ve > q0 && ve < (q0 + 64 < p1 ? q0 + 64 : p1); };
-        const int vcLast = nv * kViewStride - 1;
-        auto stagedLoad = [&](int view) {                       // lanes 0..35: the 36 doubles of views (view, view + 1)
-            const int i = view * kViewStride + (lane < 2 * kViewStride ? lane : 2 * kViewStride - 1);
-            return VC[i < vcLast ? i : vcLast];
+        // lanes 0..35: the 36 doubles of views (view, view + 1). Asked for only by a batch that holds points of both, so
+        // view + 1 exists and no index leaves VC.
+        unsigned vcOff = (unsigned)(lane < 2 * kViewStride ? lane : 2 * kViewStride - 1) * 8u;
+        auto stagedLoad = [&](int view) {
+            const T* s = VC + (int64_t)__builtin_amdgcn_readfirstlane(view) * kViewStride;
+            asm("" : "+v"(vcOff));                                // (or VC + vcOff becomes a 64-bit invariant of every lane)
+            return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(s) + vcOff);
         };
-        double vc_n = 0.0;
+        double vcx = 0.0;
         double vcs[kViewStride];                               // one-view batches: the view's constants (SGPRs)
 #pragma unroll
         for (int i = 0; i < kViewStride; ++i) vcs[i] = 0.0;
@@ -1040,7 +1063,7 @@ __global__ __launch_bounds__(64 * kFusedWaves, kStreamMinBlocks) void fused_stre
             for (int i = 0; i < kViewStride - 1; ++i) vcs[i] = s[i];
         };
         bool strad = straddles(p0, vend);
-        if (strad) vc_n = stagedLoad(va); else scalarLoad(va);
+        if (strad) vcx = stagedLoad(va); else scalarLoad(va);
         sw.request(st, sel);                                  // last: VC's address is fetched with a (short) wait of its own
         __builtin_amdgcn_sched_barrier(0);                    // everything is requested; LDS is set up behind the requests
         sw.take(sel);
@@ -1061,20 +1084,12 @@ __global__ __launch_bounds__(64 * kFusedWaves, kStreamMinBlocks) void fused_stre
         for (int q0 = p0; q0 < p1; q0 += 64) {
             const int qe = q0 + 64 < p1 ? q0 + 64 : p1;
             const int q = q0 + sl;
-            const T2 m = m_n, xy = xy_n;
-            const T z = z_n;
-            const double vcx = vc_n;
             // a boundary inside this batch (or at its start) is passed during it: what the next batch will see
             const bool more = q0 + 64 < p1;
             const bool passes = vend < qe;
             const int ve2 = passes ? vend + n : vend, va2 = passes ? va + 1 : va;
             const bool strad2 = more && straddles(q0 + 64, ve2);
             const int vfirst2 = ve2 <= q0 + 64 ? va2 + 1 : va2;
-            if (more) {
-                pn = q + 64 < p1 ? q + 64 : p1 - 1;
-                m_n = uv[pn]; xy_n = XY[pn]; z_n = Z[pn];
-                if (strad2) vc_n = stagedLoad(va2);
-            }
             T u, v;
             T2 Jc[C];
             if (!strad) {
@@ -1100,8 +1115,18 @@ __global__ __launch_bounds__(64 * kFusedWaves, kStreamMinBlocks) void fused_stre
             T2 res;
             res.x = m.x - u;
             res.y = m.y - v;
-            // the SGPRs of the view constants are free now: the next one-view batch's arrive during the contraction
+            // The registers of the points and of the view constants are free now: the next batch's arrive during the
+            // contraction. (In the order of their first reads: vector loads return in order. The scalar loads stay a
+            // statement of their own: as the else of `if (strad2)` below they land in a second set of 34 SGPRs.)
             if (more && !strad2) scalarLoad(vfirst2);
+            if (more) {
+                uvB += 64 * sizeof(T2); xyB += 64 * sizeof(T2); zB += 64 * sizeof(T);
+                pointOffsets(q0 + 64, off16, off8);
+                // (the residual is taken before its operand's registers are asked for again)
+                asm("" : "+v"(off16), "+v"(res.x), "+v"(res.y));
+                if (strad2) vcx = stagedLoad(va2);
+                xy = loadXY(); z = loadZ(); m = loadUV();
+            }
             strad = strad2;
             // chunk pairs through v_permlane32_swap: one full-width store per pair and pass (see fused_kernel, whose text
             // this repeats: a shared helper spills that kernel's fp32 forms, and the pass's stores need ch[] next to them)
