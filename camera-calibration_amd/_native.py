@@ -124,6 +124,13 @@ SIGNATURES = {
     "calib_refine_stereo": (ctypes.c_int, [_stereo_p, _c_double_p, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                            ctypes.c_double, ctypes.c_double, _c_double_p, _c_double_p, _c_int_p,
                                            _c_double_p, ctypes.c_int]),
+    "calib_stereo_joint_normal_eq": (ctypes.c_int, [_stereo_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+                                                    _c_double_p, _c_double_p, ctypes.c_int]),
+    "calib_stereo_joint_step_delta": (ctypes.c_int, [_stereo_p, _c_double_p, ctypes.c_uint64, ctypes.c_double, _c_double_p,
+                                                     ctypes.c_int]),
+    "calib_refine_stereo_joint": (ctypes.c_int, [_stereo_p, _c_double_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_double,
+                                                 ctypes.c_double, ctypes.c_double, ctypes.c_double, _c_double_p, _c_double_p,
+                                                 _c_int_p, _c_double_p, ctypes.c_int]),
     "calib_rectify_maps": (ctypes.c_int, [ctypes.c_int, _c_double_p, _c_double_p, _c_double_p, _c_double_p, ctypes.c_int,
                                           ctypes.c_int, _c_float_p, _c_float_p, ctypes.c_int]),
     "calib_rectify_points": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p,

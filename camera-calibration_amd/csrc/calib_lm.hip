@@ -4,6 +4,7 @@
 #include "kernels.hpp"
 #include "undistort.hpp"
 #include "stereo.hpp"
+#include "stereo_joint.hpp"
 #include "rectify.hpp"
 #include "host_rows.hpp"
 #include "launch_plan.hpp"
@@ -875,7 +876,7 @@ bool shared_covariance(const double* red, int L, uint32_t fixed_mask, double sig
 // ============================================================================ C-ABI
 extern "C" {
 
-int calib_version(void) { return 450; }   // 4.5: calib_rectify_maps, calib_rectify_points, calib_triangulate
+int calib_version(void) { return 460; }   // 4.6: calib_stereo_joint_normal_eq, calib_stereo_joint_step_delta, calib_refine_stereo_joint
 
 const char* calib_last_error(void) { return g_err.c_str(); }
 
@@ -2438,6 +2439,261 @@ int calib_triangulate(int model_a, const double* Aa, const double* ka, int model
     HIP_TRY(hipMemcpy(out_X, dX.p, (size_t)n * 24, hipMemcpyDeviceToHost));
     if (out_sse) HIP_TRY(hipMemcpy(out_sse, dsse.p, (size_t)n * 8, hipMemcpyDeviceToHost));
     if (out_status) HIP_TRY(hipMemcpy(out_status, dstatus.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return CALIB_OK;
+}
+
+}  // extern "C"
+
+// ---- joint stereo calibration: both cameras, the rig and the poses (stereo_joint.hpp) ------------------------------
+namespace {
+
+int joint_shared(const calib_stereo_problem_t* p) { return 16 + num_distortion(p->model_a) + num_distortion(p->model_b); }
+
+int check_stereo_joint(const calib_stereo_problem_t* p, const double* Pj, uint64_t fixed_mask) {
+    if (!p || !Pj) return fail(CALIB_E_INVALID, "null argument");
+    if (!known_model(p->model_a) || !known_model(p->model_b)) return fail(CALIB_E_INVALID, "unknown distortion model");
+    if (p->num_views < 1) return fail(CALIB_E_INVALID, "stereo calibration needs at least one view");
+    if (fixed_mask >> joint_shared(p)) return fail(CALIB_E_INVALID, "fixed_mask has a bit at or above the number of shared unknowns");
+    const int rc = check_views(p->num_views, p->offs_a, p->uv_a, p->xyz_a);
+    return rc ? rc : check_views(p->num_views, p->offs_b, p->uv_b, p->xyz_b);
+}
+
+// the two models of a joint call as compile-time shared counts
+template <typename F>
+int dispatch_joint(int model_a, int model_b, F&& f) {
+    return dispatch_model(model_a, [&](auto fa) -> int {
+        return dispatch_model(model_b, [&](auto fb) -> int { return f(fa, fb); });
+    });
+}
+
+// Device side of one joint call (StereoRun's shape): the problem, the two buffer sets the loop alternates between, the state.
+struct JointRun {
+    struct Cam {
+        DevBuf<int64_t> offs;
+        DevBuf<double2> uv;
+        DevBuf<double> xyz;
+        JointCam view() const { return JointCam{offs.p, uv.p, xyz.p}; }
+    };
+    Cam a, b;
+    DevBuf<double> Pj[2], rec[2], partA[2], tot, partC, delta, trace;
+    DevBuf<JointState> st;
+    int* done_host = nullptr;     // pinned: the decide / solve kernels set it when the loop is over
+    int64_t M = 0;
+    int nwgA = 0, nwgC = 0, model_a = 0, model_b = 0, S = 0, ntot = 0, nschur = 0;
+    JointBufs bufs{};
+    ~JointRun() { if (done_host) (void)hipHostFree(done_host); }
+
+    static int upload_cam(Cam& c, int64_t M, const int64_t* offs, const double* uv, const double* xyz) {
+        const int64_t n = offs[M];
+        HIP_TRY(c.offs.alloc((size_t)M + 1));
+        HIP_TRY(c.uv.alloc((size_t)std::max<int64_t>(n, 1)));
+        HIP_TRY(c.xyz.alloc((size_t)std::max<int64_t>(n, 1) * 3));
+        HIP_TRY(hipMemcpy(c.offs.p, offs, ((size_t)M + 1) * 8, hipMemcpyHostToDevice));
+        if (n) HIP_TRY(hipMemcpy(c.uv.p, uv, (size_t)n * 16, hipMemcpyHostToDevice));
+        if (n) HIP_TRY(hipMemcpy(c.xyz.p, xyz, (size_t)n * 24, hipMemcpyHostToDevice));
+        return CALIB_OK;
+    }
+
+    // the start point goes into buffer 0, which the bootstrap round evaluates as its candidate (cur = 1)
+    int begin(const calib_stereo_problem_t* p, const double* Pj0, uint64_t fixed_mask, int max_iters, double lam,
+              double lam_min, double lam_max, double err_min, bool want_trace, bool want_notify) {
+        M = p->num_views; model_a = p->model_a; model_b = p->model_b;
+        S = joint_shared(p);
+        nwgA = (int)((M + kJWaves - 1) / kJWaves);
+        nwgC = (int)((M + 15) / 16);
+        dispatch_joint(model_a, model_b, [&](auto fa, auto fb) -> int {
+            using Y = JointLayout<ModelTraits<decltype(fa)::MODEL>::L, ModelTraits<decltype(fb)::MODEL>::L>;
+            ntot = Y::kTot; nschur = Y::kSchur;
+            return CALIB_OK;
+        });
+        const size_t K = (size_t)S + 6 * (size_t)M;
+        int rc = upload_cam(a, M, p->offs_a, p->uv_a, p->xyz_a);
+        if (rc) return rc;
+        rc = upload_cam(b, M, p->offs_b, p->uv_b, p->xyz_b);
+        if (rc) return rc;
+        for (int s = 0; s < 2; ++s) {
+            HIP_TRY(Pj[s].alloc(K));
+            HIP_TRY(rec[s].alloc((size_t)M * kJRecord));
+            HIP_TRY(partA[s].alloc((size_t)nwgA * ntot));
+        }
+        HIP_TRY(tot.alloc(2 * (size_t)ntot));
+        HIP_TRY(partC.alloc((size_t)nwgC * nschur));
+        HIP_TRY(delta.alloc(K));
+        HIP_TRY(st.alloc(1));
+        HIP_TRY(hipMemcpy(Pj[0].p, Pj0, K * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(Pj[1].p, Pj0, K * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(tot.p, 0, 2 * (size_t)ntot * 8));
+        if (want_trace) {
+            HIP_TRY(trace.alloc((size_t)max_iters * (CALIB_TRACE_HEADER + S)));
+            HIP_TRY(hipMemset(trace.p, 0, (size_t)max_iters * (CALIB_TRACE_HEADER + S) * 8));
+        }
+        JointState s{};
+        s.lam = lam; s.lam_min = lam_min; s.lam_max = lam_max; s.err_min = err_min;
+        s.err_cur = s.last_err = std::nan("");
+        s.fixed = fixed_mask;
+        s.cur = 1; s.max_iters = max_iters;
+        if (want_notify) {
+            void* hp = nullptr; void* dp = nullptr;
+            if (hipHostMalloc(&hp, sizeof(int), hipHostMallocMapped) == hipSuccess) {
+                done_host = static_cast<int*>(hp);
+                *done_host = 0;
+                if (hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) s.notify = static_cast<int*>(dp);
+            }
+            (void)hipGetLastError();
+        }
+        HIP_TRY(hipMemcpy(st.p, &s, sizeof s, hipMemcpyHostToDevice));
+        bufs = JointBufs{{Pj[0].p, Pj[1].p}, {rec[0].p, rec[1].p}, {partA[0].p, partA[1].p}, {tot.p, tot.p + ntot},
+                         partC.p, delta.p, trace.p, st.p, M};
+        return CALIB_OK;
+    }
+
+    // blocks at the candidate, then its totals and the decision
+    int evaluate() {
+        const JointCam ca = a.view(), cb = b.view();
+        const JointBufs bf = bufs;
+        const unsigned grid = (unsigned)nwgA;
+        const int nwg = nwgA;
+        return dispatch_joint(model_a, model_b, [&](auto fa, auto fb) -> int {
+            constexpr int MA = decltype(fa)::MODEL, MB = decltype(fb)::MODEL;
+            hipLaunchKernelGGL((stereo_joint_blocks_kernel<MA, MB>), dim3(grid), dim3(64 * kJWaves), 0, 0, ca, cb, bf);
+            LAUNCHED(kNoHandle, "stereo_joint_blocks_kernel");
+            hipLaunchKernelGGL((stereo_joint_decide_kernel<ModelTraits<MA>::L, ModelTraits<MB>::L>), dim3(1), dim3(256), 0, 0,
+                               bf, nwg);
+            LAUNCHED(kNoHandle, "stereo_joint_decide_kernel");
+            return CALIB_OK;
+        });
+    }
+
+    // the step at the accepted point: Schur complement, shared solve, back-substitution into the next candidate
+    int step() {
+        const JointCam ca = a.view(), cb = b.view();
+        const JointBufs bf = bufs;
+        const int nwg = nwgC;
+        const unsigned gridB = (unsigned)((M + 63) / 64);
+        return dispatch_joint(model_a, model_b, [&](auto fa, auto fb) -> int {
+            constexpr int LA = ModelTraits<decltype(fa)::MODEL>::L, LB = ModelTraits<decltype(fb)::MODEL>::L;
+            hipLaunchKernelGGL((stereo_joint_schur_kernel<LA, LB>), dim3((unsigned)nwg), dim3(256), 0, 0, ca, cb, bf);
+            LAUNCHED(kNoHandle, "stereo_joint_schur_kernel");
+            hipLaunchKernelGGL((stereo_joint_solve_kernel<LA, LB>), dim3(1), dim3(256), 0, 0, bf, nwg);
+            LAUNCHED(kNoHandle, "stereo_joint_solve_kernel");
+            hipLaunchKernelGGL((stereo_joint_backsub_kernel<LA, LB>), dim3(gridB), dim3(64), 0, 0, bf);
+            LAUNCHED(kNoHandle, "stereo_joint_backsub_kernel");
+            return CALIB_OK;
+        });
+    }
+
+    int state(JointState& s) {
+        HIP_TRY(hipMemcpy(&s, st.p, sizeof s, hipMemcpyDeviceToHost));
+        return CALIB_OK;
+    }
+};
+
+int stereo_joint_singular() {
+    return fail(CALIB_E_SINGULAR, "joint stereo normal equations singular: a view with fewer than three points in total, or "
+                                  "a pivot of a view block or of the shared system that is not positive (a free parameter "
+                                  "that no point constrains)");
+}
+
+}  // namespace
+
+extern "C" {
+
+int calib_stereo_joint_normal_eq(const calib_stereo_problem_t* problem, const double* Pj, double* out_B, double* out_E,
+                                 double* out_V, double* out_g, double* out_sse_ab, int device_id) {
+    int rc = check_stereo_joint(problem, Pj, 0);
+    if (rc) return rc;
+    rc = use_device(device_id);
+    if (rc) return rc;
+    JointRun run;
+    rc = run.begin(problem, Pj, 0, 1, 0.0, 0.0, 0.0, 0.0, false, false);
+    if (rc) return rc;
+    rc = run.evaluate();
+    if (rc) return rc;
+    const size_t M = (size_t)problem->num_views, S = (size_t)run.S;
+    std::vector<double> rec(M * kJRecord), tot((size_t)run.ntot);
+    HIP_TRY(hipMemcpy(rec.data(), run.rec[0].p, rec.size() * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(tot.data(), run.tot.p, tot.size() * 8, hipMemcpyDeviceToHost));
+    return dispatch_joint(problem->model_a, problem->model_b, [&](auto fa, auto fb) -> int {
+        using Y = JointLayout<ModelTraits<decltype(fa)::MODEL>::L, ModelTraits<decltype(fb)::MODEL>::L>;
+        if (out_B)
+            for (int r = 0; r < Y::S; ++r)
+                for (int c = 0; c <= r; ++c) {
+                    const int slot = Y::slotB(r, c);
+                    out_B[r * S + c] = out_B[c * S + r] = slot >= 0 ? tot[(size_t)slot] : 0.0;
+                }
+        if (out_g) std::copy(tot.begin() + Y::kG, tot.begin() + Y::kG + Y::S, out_g);
+        if (out_sse_ab) { out_sse_ab[0] = tot[Y::kErr]; out_sse_ab[1] = tot[Y::kErr + 1]; }
+        for (size_t v = 0; v < M; ++v) {
+            const double* r = rec.data() + v * kJRecord;
+            if (out_V)
+                for (int i = 0; i < 6; ++i)
+                    for (int j = 0; j <= i; ++j) out_V[v * 36 + i * 6 + j] = out_V[v * 36 + j * 6 + i] = r[Y::kV + i * (i + 1) / 2 + j];
+            if (out_E) std::copy(r + Y::kE, r + Y::kE + 6 * Y::S, out_E + v * 6 * S);
+            if (out_g) std::copy(r + Y::kGv, r + Y::kGv + 6, out_g + S + v * 6);
+        }
+        return CALIB_OK;
+    });
+}
+
+int calib_stereo_joint_step_delta(const calib_stereo_problem_t* problem, const double* Pj, uint64_t fixed_mask,
+                                  double lambda, double* out_delta, int device_id) {
+    int rc = check_stereo_joint(problem, Pj, fixed_mask);
+    if (rc) return rc;
+    rc = use_device(device_id);
+    if (rc) return rc;
+    JointRun run;
+    rc = run.begin(problem, Pj, fixed_mask, 1, lambda, 0.0, 0.0, 0.0, false, false);
+    if (rc) return rc;
+    rc = run.evaluate();
+    if (rc) return rc;
+    rc = run.step();
+    if (rc) return rc;
+    JointState s;
+    rc = run.state(s);
+    if (rc) return rc;
+    if (s.error) return stereo_joint_singular();
+    if (out_delta)
+        HIP_TRY(hipMemcpy(out_delta, run.delta.p, ((size_t)run.S + 6 * (size_t)problem->num_views) * 8, hipMemcpyDeviceToHost));
+    return CALIB_OK;
+}
+
+int calib_refine_stereo_joint(const calib_stereo_problem_t* problem, double* Pj_inout, uint64_t fixed_mask, int max_iters,
+                              double lam_init, double lam_min, double lam_max, double err_min, double* out_sse,
+                              double* out_sse_ab, int* out_iters, double* out_trace, int device_id) {
+    if (max_iters <= 0) return fail(CALIB_E_INVALID, "max_iters must be >= 1");
+    int rc = check_stereo_joint(problem, Pj_inout, fixed_mask);
+    if (rc) return rc;
+    rc = use_device(device_id);
+    if (rc) return rc;
+    JointRun run;
+    rc = run.begin(problem, Pj_inout, fixed_mask, max_iters, lam_init, lam_min, lam_max, err_min, out_trace != nullptr, true);
+    if (rc) return rc;
+    // as calib_refine_stereo: round 0 evaluates the start point, round r >= 1 decides iteration r - 1; the rounds are
+    // enqueued back to back and only the done word in pinned memory is looked at
+    JointState s;
+    for (int r = 0; r <= max_iters; ++r) {
+        rc = run.evaluate();
+        if (rc) return rc;
+        rc = run.step();
+        if (rc) return rc;
+        if (run.done_host) {
+            if (*static_cast<volatile int*>(run.done_host)) break;
+        } else if ((r + 1) % 8 == 0) {
+            rc = run.state(s);
+            if (rc) return rc;
+            if (s.done) break;
+        }
+    }
+    rc = run.state(s);
+    if (rc) return rc;
+    if (s.error) return stereo_joint_singular();
+    const size_t K = (size_t)run.S + 6 * (size_t)problem->num_views;
+    const size_t W = (size_t)(CALIB_TRACE_HEADER + run.S);
+    HIP_TRY(hipMemcpy(Pj_inout, run.Pj[s.cur].p, K * 8, hipMemcpyDeviceToHost));
+    if (out_sse) *out_sse = s.last_err;
+    if (out_iters) *out_iters = s.iters;
+    if (out_sse_ab) HIP_TRY(hipMemcpy(out_sse_ab, run.tot.p + (size_t)s.cur * run.ntot + (run.ntot - 2), 16, hipMemcpyDeviceToHost));
+    if (out_trace && s.iters > 0) HIP_TRY(hipMemcpy(out_trace, run.trace.p, (size_t)s.iters * W * 8, hipMemcpyDeviceToHost));
     return CALIB_OK;
 }
 

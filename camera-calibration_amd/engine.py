@@ -832,6 +832,61 @@ def refineStereo(cameraA, cameraB, Ps0, maxIters, lamInit=LAMBDA_INITIAL, lamMin
     return sse.value, Ps, iters.value, trace[:iters.value], (float(ab[0]), float(ab[1]))
 
 
+# ---- joint stereo calibration: cameras, rig and poses together (calib_stereo_joint_*, csrc/stereo_joint.hpp) ------------
+def stereoJointShared(cameraA, cameraB):
+    """S = La + Lb + 6, the number of shared unknowns of the joint problem of two cameras (_stereoProblem's tuples)"""
+    return NUM_SHARED[cameraA[0]] + NUM_SHARED[cameraB[0]] + 6
+
+
+def _stereoJoint(cameraA, cameraB, Pj, fixedMask=0):
+    """-> (the C struct, what it points into, M, S, Pj (S + 6 M,), mask). The cameras' own shared vectors are not read
+    by the joint calls: the cameras travel in Pj = (shared_a, shared_b, rig, pose_0, ..)."""
+    prob, keep, M = _stereoProblem(cameraA, cameraB)
+    S = stereoJointShared(cameraA, cameraB)
+    Pj = np.ascontiguousarray(np.asarray(Pj, dtype=np.float64).ravel())
+    if Pj.shape[0] != S + 6 * M:
+        raise ValueError(f"Expected shape ({S + 6 * M},) = ({S} shared, {M} poses), got {Pj.shape}")
+    mask = int(fixedMask)
+    if mask < 0 or mask >> S:
+        raise ValueError(f"fixed mask {mask:#x} has bits outside the {S} shared unknowns")
+    return prob, keep, M, S, Pj, mask
+
+
+def stereoJointNormalEquations(cameraA, cameraB, Pj, device=0):
+    """Block-arrow normal equations of the joint stereo problem at Pj -> dict B (S,S), E (M,S,6) [shared row, view
+    column], V (M,6,6), g (S + 6 M,), sseA, sseB."""
+    prob, keep, M, S, Pj, _ = _stereoJoint(cameraA, cameraB, Pj)
+    B, E, V, g, ab = np.empty((S, S)), np.empty((M, S, 6)), np.empty((M, 6, 6)), np.empty(S + 6 * M), np.empty(2)
+    nat.check(nat.loadLibrary().calib_stereo_joint_normal_eq(ctypes.byref(prob), nat.dptr(Pj), nat.dptr(B), nat.dptr(E),
+                                                             nat.dptr(V), nat.dptr(g), nat.dptr(ab), int(device)))
+    return {"B": B, "E": E, "V": V, "g": g, "sseA": float(ab[0]), "sseB": float(ab[1])}
+
+
+def stereoJointStepDelta(cameraA, cameraB, Pj, lam, fixedMask=0, device=0):
+    """delta (S + 6 M,) = the LM step of the joint stereo problem at Pj with the shared unknowns of fixedMask held,
+    solved on the device."""
+    prob, keep, M, S, Pj, mask = _stereoJoint(cameraA, cameraB, Pj, fixedMask)
+    delta = np.empty(S + 6 * M)
+    nat.check(nat.loadLibrary().calib_stereo_joint_step_delta(ctypes.byref(prob), nat.dptr(Pj), mask, float(lam),
+                                                              nat.dptr(delta), int(device)))
+    return delta
+
+
+def refineStereoJoint(cameraA, cameraB, Pj0, maxIters, fixedMask=0, lamInit=LAMBDA_INITIAL, lamMin=LAMBDA_MIN,
+                      lamMax=LAMBDA_MAX, errMin=PT_ERROR_MIN, device=0):
+    """The LM loop on Pj = (shared_a, shared_b, rig, pose_0, ..) -> (sse [pre-update, as the reference returns], Pj,
+    iters, trace (iters, 5 + S), (sseA, sseB) at the returned Pj)."""
+    prob, keep, M, S, Pj, mask = _stereoJoint(cameraA, cameraB, Pj0, fixedMask)
+    Pj = Pj.copy()
+    maxIters = int(maxIters)
+    sse, iters, ab = ctypes.c_double(0.0), ctypes.c_int(0), np.empty(2)
+    trace = np.zeros((max(maxIters, 1), nat.TRACE_HEADER + S))
+    nat.check(nat.loadLibrary().calib_refine_stereo_joint(
+        ctypes.byref(prob), nat.dptr(Pj), mask, maxIters, float(lamInit), float(lamMin), float(lamMax), float(errMin),
+        ctypes.byref(sse), nat.dptr(ab), ctypes.byref(iters), nat.dptr(trace), int(device)))
+    return sse.value, Pj, iters.value, trace[:iters.value], (float(ab[0]), float(ab[1]))
+
+
 # ---- using a calibrated rig (calib_rectify_*, calib_triangulate, csrc/rectify.hpp): arguments are checked first --------
 def _rotation(R, name="R"):
     if R is None:

@@ -408,6 +408,32 @@ int calib_refine_stereo(const calib_stereo_problem_t* problem, double* Ps_inout,
                         double lam_min, double lam_max, double err_min, double* out_sse, double* out_sse_ab,
                         int* out_iters, double* out_trace, int device_id);
 
+/* ---- joint stereo calibration: both cameras, the rig and the board poses in one problem ---------------------------
+ * The problem of calib_refine_stereo with the two cameras free. Unknowns Pj (S + 6 M) = (shared_a[La], shared_b[Lb],
+ * rig[6], pose_0[6], .., pose_{M-1}[6]), S = La + Lb + 6 <= 26, the shared vectors in the order of P, the 6-tuples as in
+ * Ps. The struct's shared_a / shared_b are not read and may be NULL: the cameras travel in Pj. fixed_mask: bit s set
+ * holds shared unknown s (camera a's, then camera b's, then the rig's) fixed by the rule of calib_lm_begin's mask -- the
+ * reduced S x S system is edited, the parameter keeps its bits; a bit at or above S is CALIB_E_INVALID. With all
+ * La + Lb camera bits set the problem is calib_refine_stereo's. Stateless, fixed-order sums, argument checks before
+ * any device call as for the calls above.
+ *
+ * calib_stereo_joint_normal_eq: out_B (S,S) -- its shared_a x (shared_b, rig) block is exactly zero --, out_E (M,S,6)
+ *   shared row x view column, out_V (M,6,6), out_g (S + 6 M) = J^T r in the order of Pj, out_sse_ab (2).
+ * calib_stereo_joint_step_delta: delta (S + 6 M) = the LM step at Pj through the Schur complement of the view blocks;
+ *   0 at fixed parameters.
+ * calib_refine_stereo_joint: the loop of calib_refine_stereo on Pj; out_trace rows are CALIB_TRACE_HEADER + S doubles,
+ *   the shared unknowns before the update.
+ * CALIB_E_SINGULAR (Pj_inout left as it was): a view with fewer than three points in total, an empty view, a pivot of
+ *   a view block or of the reduced system that is not positive -- a free camera that sees nothing, for one; the same
+ *   problem with that camera's bits all set succeeds. */
+int calib_stereo_joint_normal_eq(const calib_stereo_problem_t* problem, const double* Pj, double* out_B, double* out_E,
+                                 double* out_V, double* out_g, double* out_sse_ab, int device_id);
+int calib_stereo_joint_step_delta(const calib_stereo_problem_t* problem, const double* Pj, uint64_t fixed_mask,
+                                  double lambda, double* out_delta, int device_id);
+int calib_refine_stereo_joint(const calib_stereo_problem_t* problem, double* Pj_inout, uint64_t fixed_mask, int max_iters,
+                              double lam_init, double lam_min, double lam_max, double err_min, double* out_sse,
+                              double* out_sse_ab, int* out_iters, double* out_trace, int device_id);
+
 /* ---- using a calibrated rig: rectify maps, rectified points, triangulation ---------------------------------------
  * Stateless, host pointers, the work runs on device_id; cameras as in the undistortion entries (A (3,3) row-major, k the
  * model's coefficients). R is a (3,3) row-major rotation; |det R - 1| > 1e-6 is CALIB_E_INVALID, as are a bad model id, a
