@@ -55,7 +55,9 @@ def _estimateHomographyBatch(Xa, Xb):
         M[:, 0::2, 6], M[:, 0::2, 7], M[:, 0::2, 8] = u * X, u * Y, u
         M[:, 1::2, 3], M[:, 1::2, 4], M[:, 1::2, 5] = -X, -Y, -1.0
         M[:, 1::2, 6], M[:, 1::2, 7], M[:, 1::2, 8] = v * X, v * Y, v
-        Vt = np.linalg.svd(M, full_matrices=False)[2]
+        # a view of 4 points has an 8 x 9 M: its null vector is the ninth row of the full V^T (which the
+        # reference always computes), not the last of the 8 rows of the reduced one
+        Vt = np.linalg.svd(M, full_matrices=2 * N < 9)[2]
         Hp = Vt[:, -1, :].reshape(B, 3, 3)
     else:
         # the same vector as the eigenvector of M^T M of the smallest eigenvalue, with M^T M built
