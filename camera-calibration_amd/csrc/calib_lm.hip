@@ -2063,17 +2063,57 @@ int calib_remap(int dtype, const void* src, int src_h, int src_w, int channels, 
 
 }  // extern "C"
 
-// ---- stereo calibration with both cameras known (stereo.hpp) ------------------------------------
+// ---- stereo calibration: the host side of the LM loop both solvers share (stereo_loop.hpp), then the rig-only solver
+// ---- with both cameras known (stereo.hpp); the joint solver's own part follows the rectification section
 namespace {
 
-int check_stereo(const calib_stereo_problem_t* p, const double* Ps) {
-    if (!p || !Ps) return fail(CALIB_E_INVALID, "null argument");
+struct StereoRun;
+
+// What differs between the two solvers on the host: the sizes of a problem's buffers and the launches of a round.
+struct StereoSolver {
+    int S;                  // shared unknowns: the rig's 6, or LA + LB + 6
+    int record;             // doubles per view record
+    int ntot, nschur;       // entries per workgroup partial of the blocks / of the Schur kernel
+    int views_a;            // views per workgroup of the blocks kernel (the Schur kernel: 16)
+    int (*evaluate)(const StereoRun&);      // blocks at the candidate, then its totals and the decision
+    int (*step)(const StereoRun&);          // at the accepted point: Schur complement, shared solve, back-substitution
+    int (*singular)();                      // the solver's CALIB_E_SINGULAR
+};
+StereoSolver rig_solver();
+StereoSolver joint_solver(int model_a, int model_b);
+int joint_shared(const calib_stereo_problem_t* p) { return 16 + num_distortion(p->model_a) + num_distortion(p->model_b); }
+
+// The rig-only solver reads the cameras from the problem; the joint one has them in P and adds the mask test.
+int check_stereo(const calib_stereo_problem_t* p, const double* P, bool joint, uint64_t fixed_mask) {
+    if (!p || !P) return fail(CALIB_E_INVALID, "null argument");
     if (!known_model(p->model_a) || !known_model(p->model_b)) return fail(CALIB_E_INVALID, "unknown distortion model");
     if (p->num_views < 1) return fail(CALIB_E_INVALID, "stereo calibration needs at least one view");
-    if (!p->shared_a || !p->shared_b) return fail(CALIB_E_INVALID, "null argument");
+    if (!joint && (!p->shared_a || !p->shared_b)) return fail(CALIB_E_INVALID, "null argument");
+    if (joint && fixed_mask >> joint_shared(p)) return fail(CALIB_E_INVALID, "fixed_mask has a bit at or above the number of shared unknowns");
     const int rc = check_views(p->num_views, p->offs_a, p->uv_a, p->xyz_a);
     return rc ? rc : check_views(p->num_views, p->offs_b, p->uv_b, p->xyz_b);
 }
+
+// A word in pinned memory that the device sets when the loop is over. Best effort: without it (or without its device
+// address) the host looks at the state instead.
+struct DoneWord {
+    int* host = nullptr;
+    int* dev = nullptr;
+    DoneWord() = default;
+    DoneWord(const DoneWord&) = delete;
+    DoneWord& operator=(const DoneWord&) = delete;
+    ~DoneWord() { if (host) (void)hipHostFree(host); }
+    void create() {
+        void* hp = nullptr; void* dp = nullptr;
+        if (hipHostMalloc(&hp, sizeof(int), hipHostMallocMapped) == hipSuccess) {
+            host = static_cast<int*>(hp);
+            *host = 0;
+            if (hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) dev = static_cast<int*>(dp);
+        }
+        (void)hipGetLastError();
+    }
+    bool set() const { return *static_cast<volatile int*>(host) != 0; }
+};
 
 // Device side of one stereo call: the problem, the two (point, record, total) buffer sets the loop alternates between,
 // the state. Released with the scope of the entry point.
@@ -2081,17 +2121,20 @@ struct StereoRun {
     struct Cam {
         DevBuf<int64_t> offs;
         DevBuf<double2> uv;
-        DevBuf<double> xyz, shared;
-        StereoCam view() const { return StereoCam{offs.p, uv.p, xyz.p, shared.p}; }
+        DevBuf<double> xyz, shared;         // shared: the rig-only solver's known camera
+        StereoCam view() const { return StereoCam{offs.p, uv.p, xyz.p}; }
     };
+    StereoSolver sv{};
     Cam a, b;
-    DevBuf<double> Ps[2], rec[2], partA[2], tot, partC, delta, trace;
+    DevBuf<double> P[2], rec[2], partA[2], tot, partC, delta, trace;
     DevBuf<StereoState> st;
-    int* done_host = nullptr;     // pinned: the decide / rig kernels set it when the loop is over
+    DoneWord done;
     int64_t M = 0;
-    int nwg = 0, model_a = 0, model_b = 0;
+    int nwgA = 0, nwgC = 0, model_a = 0, model_b = 0;
     StereoBufs bufs{};
-    ~StereoRun() { if (done_host) (void)hipHostFree(done_host); }
+
+    size_t params() const { return (size_t)sv.S + 6 * (size_t)M; }
+    size_t trace_width() const { return (size_t)(CALIB_TRACE_HEADER + sv.S); }
 
     static int upload_cam(Cam& c, int model, int64_t M, const int64_t* offs, const double* uv, const double* xyz,
                           const double* shared) {
@@ -2100,179 +2143,133 @@ struct StereoRun {
         HIP_TRY(c.offs.alloc((size_t)M + 1));
         HIP_TRY(c.uv.alloc((size_t)std::max<int64_t>(n, 1)));
         HIP_TRY(c.xyz.alloc((size_t)std::max<int64_t>(n, 1) * 3));
-        HIP_TRY(c.shared.alloc(L));
         HIP_TRY(hipMemcpy(c.offs.p, offs, ((size_t)M + 1) * 8, hipMemcpyHostToDevice));
         if (n) HIP_TRY(hipMemcpy(c.uv.p, uv, (size_t)n * 16, hipMemcpyHostToDevice));
         if (n) HIP_TRY(hipMemcpy(c.xyz.p, xyz, (size_t)n * 24, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c.shared.p, shared, L * 8, hipMemcpyHostToDevice));
+        if (shared) {
+            HIP_TRY(c.shared.alloc(L));
+            HIP_TRY(hipMemcpy(c.shared.p, shared, L * 8, hipMemcpyHostToDevice));
+        }
         return CALIB_OK;
     }
 
     // the start point goes into buffer 0, which the bootstrap round evaluates as its candidate (cur = 1)
-    int begin(const calib_stereo_problem_t* p, const double* Ps0, int max_iters, double lam, double lam_min,
-              double lam_max, double err_min, bool want_trace, bool want_notify) {
+    int begin(const StereoSolver& solver, bool joint, const calib_stereo_problem_t* p, const double* P0, uint64_t fixed_mask,
+              int max_iters, double lam, double lam_min, double lam_max, double err_min, bool want_trace, bool want_notify) {
+        sv = solver;
         M = p->num_views; model_a = p->model_a; model_b = p->model_b;
-        nwg = (int)((M + 15) / 16);
-        const size_t K = 6 + 6 * (size_t)M;
-        int rc = upload_cam(a, p->model_a, M, p->offs_a, p->uv_a, p->xyz_a, p->shared_a);
+        nwgA = (int)((M + sv.views_a - 1) / sv.views_a);
+        nwgC = (int)((M + 15) / 16);
+        const size_t K = params();
+        int rc = upload_cam(a, p->model_a, M, p->offs_a, p->uv_a, p->xyz_a, joint ? nullptr : p->shared_a);
         if (rc) return rc;
-        rc = upload_cam(b, p->model_b, M, p->offs_b, p->uv_b, p->xyz_b, p->shared_b);
+        rc = upload_cam(b, p->model_b, M, p->offs_b, p->uv_b, p->xyz_b, joint ? nullptr : p->shared_b);
         if (rc) return rc;
         for (int s = 0; s < 2; ++s) {
-            HIP_TRY(Ps[s].alloc(K));
-            HIP_TRY(rec[s].alloc((size_t)M * kStRecord));
-            HIP_TRY(partA[s].alloc((size_t)nwg * kStTot));
+            HIP_TRY(P[s].alloc(K));
+            HIP_TRY(rec[s].alloc((size_t)M * sv.record));
+            HIP_TRY(partA[s].alloc((size_t)nwgA * sv.ntot));
         }
-        HIP_TRY(tot.alloc(2 * kStTot));
-        HIP_TRY(partC.alloc((size_t)nwg * kStSchur));
+        HIP_TRY(tot.alloc(2 * (size_t)sv.ntot));
+        HIP_TRY(partC.alloc((size_t)nwgC * sv.nschur));
         HIP_TRY(delta.alloc(K));
         HIP_TRY(st.alloc(1));
-        HIP_TRY(hipMemcpy(Ps[0].p, Ps0, K * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(Ps[1].p, Ps0, K * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemset(tot.p, 0, 2 * kStTot * 8));
+        HIP_TRY(hipMemcpy(P[0].p, P0, K * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(P[1].p, P0, K * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(tot.p, 0, 2 * (size_t)sv.ntot * 8));
         if (want_trace) {
-            HIP_TRY(trace.alloc((size_t)max_iters * kStTrace));
-            HIP_TRY(hipMemset(trace.p, 0, (size_t)max_iters * kStTrace * 8));
+            HIP_TRY(trace.alloc((size_t)max_iters * trace_width()));
+            HIP_TRY(hipMemset(trace.p, 0, (size_t)max_iters * trace_width() * 8));
         }
         StereoState s{};
         s.lam = lam; s.lam_min = lam_min; s.lam_max = lam_max; s.err_min = err_min;
         s.err_cur = s.last_err = std::nan("");
+        s.fixed = fixed_mask;
         s.cur = 1; s.max_iters = max_iters;
         if (want_notify) {
-            void* hp = nullptr; void* dp = nullptr;
-            if (hipHostMalloc(&hp, sizeof(int), hipHostMallocMapped) == hipSuccess) {
-                done_host = static_cast<int*>(hp);
-                *done_host = 0;
-                if (hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) s.notify = static_cast<int*>(dp);
-            }
-            (void)hipGetLastError();
+            done.create();
+            s.notify = done.dev;
         }
         HIP_TRY(hipMemcpy(st.p, &s, sizeof s, hipMemcpyHostToDevice));
-        bufs = StereoBufs{{Ps[0].p, Ps[1].p}, {rec[0].p, rec[1].p}, {partA[0].p, partA[1].p}, {tot.p, tot.p + kStTot},
+        bufs = StereoBufs{{P[0].p, P[1].p}, {rec[0].p, rec[1].p}, {partA[0].p, partA[1].p}, {tot.p, tot.p + sv.ntot},
                           partC.p, delta.p, trace.p, st.p, M};
         return CALIB_OK;
     }
 
-    // blocks at the candidate, then its totals and the decision
-    int evaluate() {
-        const StereoCam ca = a.view(), cb = b.view();
-        const StereoBufs bf = bufs;
-        const unsigned grid = (unsigned)nwg;
-        const int rc = dispatch_model(model_a, [&](auto fa) -> int {
-            return dispatch_model(model_b, [&](auto fb) -> int {
-                hipLaunchKernelGGL((stereo_blocks_kernel<decltype(fa)::MODEL, decltype(fb)::MODEL>), dim3(grid), dim3(256),
-                                   0, 0, ca, cb, bf);
-                LAUNCHED(kNoHandle, "stereo_blocks_kernel");
-                return CALIB_OK;
-            });
-        });
-        if (rc) return rc;
-        hipLaunchKernelGGL(stereo_decide_kernel<kStTot>, dim3(1), dim3(256), 0, 0, bf, nwg);
-        LAUNCHED(kNoHandle, "stereo_decide_kernel");
-        return CALIB_OK;
-    }
-
-    // the step at the accepted point: Schur complement, rig solve, back-substitution into the next candidate
-    int step() {
-        const StereoBufs bf = bufs;
-        hipLaunchKernelGGL(stereo_schur_kernel<16>, dim3((unsigned)nwg), dim3(256), 0, 0, a.view(), b.view(), bf);
-        LAUNCHED(kNoHandle, "stereo_schur_kernel");
-        hipLaunchKernelGGL(stereo_rig_kernel<kStSchur>, dim3(1), dim3(256), 0, 0, bf, nwg);
-        LAUNCHED(kNoHandle, "stereo_rig_kernel");
-        hipLaunchKernelGGL(stereo_backsub_kernel<64>, dim3((unsigned)((M + 63) / 64)), dim3(64), 0, 0, bf);
-        LAUNCHED(kNoHandle, "stereo_backsub_kernel");
-        return CALIB_OK;
-    }
-
-    int state(StereoState& s) {
+    int state(StereoState& s) const {
         HIP_TRY(hipMemcpy(&s, st.p, sizeof s, hipMemcpyDeviceToHost));
         return CALIB_OK;
     }
 };
 
-int stereo_singular() {
-    return fail(CALIB_E_SINGULAR, "stereo normal equations singular: a view with fewer than three points in total or a "
-                                  "pivot that is not positive, or a rig that no view with points in camera b constrains");
-}
-
-}  // namespace
-
-extern "C" {
-
-int calib_stereo_normal_eq(const calib_stereo_problem_t* problem, const double* Ps, double* out_B, double* out_E,
-                           double* out_V, double* out_g, double* out_sse_ab, int device_id) {
-    int rc = check_stereo(problem, Ps);
+// checks, device, solver and the run's buffers with P as the start point
+int stereo_begin(StereoRun& run, bool joint, const calib_stereo_problem_t* p, const double* P, uint64_t fixed_mask,
+                 int max_iters, double lam, double lam_min, double lam_max, double err_min, bool want_trace, bool want_notify,
+                 int device_id) {
+    int rc = check_stereo(p, P, joint, fixed_mask);
     if (rc) return rc;
     rc = use_device(device_id);
     if (rc) return rc;
-    StereoRun run;
-    rc = run.begin(problem, Ps, 1, 0.0, 0.0, 0.0, 0.0, false, false);
+    return run.begin(joint ? joint_solver(p->model_a, p->model_b) : rig_solver(), joint, p, P, fixed_mask, max_iters, lam,
+                     lam_min, lam_max, err_min, want_trace, want_notify);
+}
+
+// the blocks at P on the host: every view's record and the totals
+int stereo_blocks(StereoRun& run, bool joint, const calib_stereo_problem_t* p, const double* P, int device_id,
+                  std::vector<double>& rec, std::vector<double>& tot) {
+    int rc = stereo_begin(run, joint, p, P, 0, 1, 0.0, 0.0, 0.0, 0.0, false, false, device_id);
     if (rc) return rc;
-    rc = run.evaluate();
+    rc = run.sv.evaluate(run);
     if (rc) return rc;
-    const size_t M = (size_t)problem->num_views;
-    std::vector<double> rec(M * kStRecord), tot(kStTot);
+    rec.resize((size_t)run.M * run.sv.record);
+    tot.resize((size_t)run.sv.ntot);
     HIP_TRY(hipMemcpy(rec.data(), run.rec[0].p, rec.size() * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(tot.data(), run.tot.p, kStTot * 8, hipMemcpyDeviceToHost));
-    auto sym = [](const double* t, double* o) {
-        for (int r = 0; r < 6; ++r)
-            for (int c = 0; c <= r; ++c) o[r * 6 + c] = o[c * 6 + r] = t[r * (r + 1) / 2 + c];
-    };
-    if (out_B) sym(tot.data(), out_B);
-    if (out_g) std::copy(tot.begin() + 21, tot.begin() + 27, out_g);
-    if (out_sse_ab) { out_sse_ab[0] = tot[27]; out_sse_ab[1] = tot[28]; }
-    for (size_t v = 0; v < M; ++v) {
-        const double* r = rec.data() + v * kStRecord;
-        if (out_V) sym(r + kStV, out_V + v * 36);
-        if (out_E) std::copy(r + kStE, r + kStE + 36, out_E + v * 36);
-        if (out_g) std::copy(r + kStGv, r + kStGv + 6, out_g + 6 + v * 6);
-    }
+    HIP_TRY(hipMemcpy(tot.data(), run.tot.p, tot.size() * 8, hipMemcpyDeviceToHost));
     return CALIB_OK;
 }
 
-int calib_stereo_step_delta(const calib_stereo_problem_t* problem, const double* Ps, double lambda, double* out_delta,
-                            int device_id) {
-    int rc = check_stereo(problem, Ps);
-    if (rc) return rc;
-    rc = use_device(device_id);
-    if (rc) return rc;
+// a 6 x 6 lower triangle stored row by row -> the full symmetric matrix
+void sym6(const double* t, double* o) {
+    for (int r = 0; r < 6; ++r)
+        for (int c = 0; c <= r; ++c) o[r * 6 + c] = o[c * 6 + r] = t[r * (r + 1) / 2 + c];
+}
+
+int stereo_step_delta(bool joint, const calib_stereo_problem_t* p, const double* P, uint64_t fixed_mask, double lambda,
+                      double* out_delta, int device_id) {
     StereoRun run;
-    rc = run.begin(problem, Ps, 1, lambda, 0.0, 0.0, 0.0, false, false);
+    int rc = stereo_begin(run, joint, p, P, fixed_mask, 1, lambda, 0.0, 0.0, 0.0, false, false, device_id);
     if (rc) return rc;
-    rc = run.evaluate();
+    rc = run.sv.evaluate(run);
     if (rc) return rc;
-    rc = run.step();
+    rc = run.sv.step(run);
     if (rc) return rc;
     StereoState s;
     rc = run.state(s);
     if (rc) return rc;
-    if (s.error) return stereo_singular();
-    if (out_delta) HIP_TRY(hipMemcpy(out_delta, run.delta.p, (6 + 6 * (size_t)problem->num_views) * 8, hipMemcpyDeviceToHost));
+    if (s.error) return run.sv.singular();
+    if (out_delta) HIP_TRY(hipMemcpy(out_delta, run.delta.p, run.params() * 8, hipMemcpyDeviceToHost));
     return CALIB_OK;
 }
 
-int calib_refine_stereo(const calib_stereo_problem_t* problem, double* Ps_inout, int max_iters, double lam_init,
-                        double lam_min, double lam_max, double err_min, double* out_sse, double* out_sse_ab,
-                        int* out_iters, double* out_trace, int device_id) {
+int stereo_refine(bool joint, const calib_stereo_problem_t* p, double* P_inout, uint64_t fixed_mask, int max_iters,
+                  double lam_init, double lam_min, double lam_max, double err_min, double* out_sse, double* out_sse_ab,
+                  int* out_iters, double* out_trace, int device_id) {
     if (max_iters <= 0) return fail(CALIB_E_INVALID, "max_iters must be >= 1");
-    int rc = check_stereo(problem, Ps_inout);
-    if (rc) return rc;
-    rc = use_device(device_id);
-    if (rc) return rc;
     StereoRun run;
-    rc = run.begin(problem, Ps_inout, max_iters, lam_init, lam_min, lam_max, err_min, out_trace != nullptr, true);
+    int rc = stereo_begin(run, joint, p, P_inout, fixed_mask, max_iters, lam_init, lam_min, lam_max, err_min,
+                          out_trace != nullptr, true, device_id);
     if (rc) return rc;
     // round 0 evaluates the start point; round r >= 1 decides iteration r - 1. The host runs ahead of the device: the
     // done word in pinned memory stops the enqueueing (rounds already in the queue return at once); without such a word,
     // a synchronised look at the state every 8 rounds.
     StereoState s;
     for (int r = 0; r <= max_iters; ++r) {
-        rc = run.evaluate();
+        rc = run.sv.evaluate(run);
         if (rc) return rc;
-        rc = run.step();
+        rc = run.sv.step(run);
         if (rc) return rc;
-        if (run.done_host) {
-            if (*static_cast<volatile int*>(run.done_host)) break;
+        if (run.done.host) {
+            if (run.done.set()) break;
         } else if ((r + 1) % 8 == 0) {
             rc = run.state(s);
             if (rc) return rc;
@@ -2281,15 +2278,85 @@ int calib_refine_stereo(const calib_stereo_problem_t* problem, double* Ps_inout,
     }
     rc = run.state(s);
     if (rc) return rc;
-    if (s.error) return stereo_singular();
-    const size_t K = 6 + 6 * (size_t)problem->num_views;
-    HIP_TRY(hipMemcpy(Ps_inout, run.Ps[s.cur].p, K * 8, hipMemcpyDeviceToHost));
+    if (s.error) return run.sv.singular();
+    HIP_TRY(hipMemcpy(P_inout, run.P[s.cur].p, run.params() * 8, hipMemcpyDeviceToHost));
     if (out_sse) *out_sse = s.last_err;
     if (out_iters) *out_iters = s.iters;
-    if (out_sse_ab) HIP_TRY(hipMemcpy(out_sse_ab, run.tot.p + s.cur * kStTot + 27, 16, hipMemcpyDeviceToHost));
+    if (out_sse_ab)     // the two errors end the totals
+        HIP_TRY(hipMemcpy(out_sse_ab, run.tot.p + (size_t)s.cur * run.sv.ntot + (run.sv.ntot - 2), 16, hipMemcpyDeviceToHost));
     if (out_trace && s.iters > 0)
-        HIP_TRY(hipMemcpy(out_trace, run.trace.p, (size_t)s.iters * kStTrace * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out_trace, run.trace.p, (size_t)s.iters * run.trace_width() * 8, hipMemcpyDeviceToHost));
     return CALIB_OK;
+}
+
+int rig_evaluate(const StereoRun& r) {
+    const StereoCam ca = r.a.view(), cb = r.b.view();
+    const StereoBufs bf = r.bufs;
+    const unsigned grid = (unsigned)r.nwgA;
+    const int rc = dispatch_model(r.model_a, [&](auto fa) -> int {
+        return dispatch_model(r.model_b, [&](auto fb) -> int {
+            hipLaunchKernelGGL((stereo_blocks_kernel<decltype(fa)::MODEL, decltype(fb)::MODEL>), dim3(grid), dim3(256),
+                               0, 0, ca, r.a.shared.p, cb, r.b.shared.p, bf);
+            LAUNCHED(kNoHandle, "stereo_blocks_kernel");
+            return CALIB_OK;
+        });
+    });
+    if (rc) return rc;
+    hipLaunchKernelGGL(stereo_decide_kernel<kStTot>, dim3(1), dim3(256), 0, 0, bf, r.nwgA);
+    LAUNCHED(kNoHandle, "stereo_decide_kernel");
+    return CALIB_OK;
+}
+
+int rig_step(const StereoRun& r) {
+    const StereoBufs bf = r.bufs;
+    hipLaunchKernelGGL(stereo_schur_kernel<16>, dim3((unsigned)r.nwgC), dim3(256), 0, 0, r.a.view(), r.b.view(), bf);
+    LAUNCHED(kNoHandle, "stereo_schur_kernel");
+    hipLaunchKernelGGL(stereo_rig_kernel<kStSchur>, dim3(1), dim3(256), 0, 0, bf, r.nwgC);
+    LAUNCHED(kNoHandle, "stereo_rig_kernel");
+    hipLaunchKernelGGL((stereo_backsub_kernel<StereoRecord, 6>), dim3((unsigned)((r.M + 63) / 64)), dim3(64), 0, 0, bf);
+    LAUNCHED(kNoHandle, "stereo_backsub_kernel");
+    return CALIB_OK;
+}
+
+int stereo_singular() {
+    return fail(CALIB_E_SINGULAR, "stereo normal equations singular: a view with fewer than three points in total or a "
+                                  "pivot that is not positive, or a rig that no view with points in camera b constrains");
+}
+
+StereoSolver rig_solver() { return StereoSolver{6, kStRecord, kStTot, kStSchur, 16, rig_evaluate, rig_step, stereo_singular}; }
+
+}  // namespace
+
+extern "C" {
+
+int calib_stereo_normal_eq(const calib_stereo_problem_t* problem, const double* Ps, double* out_B, double* out_E,
+                           double* out_V, double* out_g, double* out_sse_ab, int device_id) {
+    StereoRun run;
+    std::vector<double> rec, tot;
+    const int rc = stereo_blocks(run, false, problem, Ps, device_id, rec, tot);
+    if (rc) return rc;
+    if (out_B) sym6(tot.data(), out_B);
+    if (out_g) std::copy(tot.begin() + 21, tot.begin() + 27, out_g);
+    if (out_sse_ab) { out_sse_ab[0] = tot[27]; out_sse_ab[1] = tot[28]; }
+    for (size_t v = 0; v < (size_t)problem->num_views; ++v) {
+        const double* r = rec.data() + v * kStRecord;
+        if (out_V) sym6(r + kStV, out_V + v * 36);
+        if (out_E) std::copy(r + kStE, r + kStE + 36, out_E + v * 36);
+        if (out_g) std::copy(r + kStGv, r + kStGv + 6, out_g + 6 + v * 6);
+    }
+    return CALIB_OK;
+}
+
+int calib_stereo_step_delta(const calib_stereo_problem_t* problem, const double* Ps, double lambda, double* out_delta,
+                            int device_id) {
+    return stereo_step_delta(false, problem, Ps, 0, lambda, out_delta, device_id);
+}
+
+int calib_refine_stereo(const calib_stereo_problem_t* problem, double* Ps_inout, int max_iters, double lam_init,
+                        double lam_min, double lam_max, double err_min, double* out_sse, double* out_sse_ab,
+                        int* out_iters, double* out_trace, int device_id) {
+    return stereo_refine(false, problem, Ps_inout, 0, max_iters, lam_init, lam_min, lam_max, err_min, out_sse, out_sse_ab,
+                         out_iters, out_trace, device_id);
 }
 
 }  // extern "C"
@@ -2444,19 +2511,8 @@ int calib_triangulate(int model_a, const double* Aa, const double* ka, int model
 
 }  // extern "C"
 
-// ---- joint stereo calibration: both cameras, the rig and the poses (stereo_joint.hpp) ------------------------------
+// ---- joint stereo calibration: both cameras, the rig and the poses (stereo_joint.hpp); the loop is the section's above
 namespace {
-
-int joint_shared(const calib_stereo_problem_t* p) { return 16 + num_distortion(p->model_a) + num_distortion(p->model_b); }
-
-int check_stereo_joint(const calib_stereo_problem_t* p, const double* Pj, uint64_t fixed_mask) {
-    if (!p || !Pj) return fail(CALIB_E_INVALID, "null argument");
-    if (!known_model(p->model_a) || !known_model(p->model_b)) return fail(CALIB_E_INVALID, "unknown distortion model");
-    if (p->num_views < 1) return fail(CALIB_E_INVALID, "stereo calibration needs at least one view");
-    if (fixed_mask >> joint_shared(p)) return fail(CALIB_E_INVALID, "fixed_mask has a bit at or above the number of shared unknowns");
-    const int rc = check_views(p->num_views, p->offs_a, p->uv_a, p->xyz_a);
-    return rc ? rc : check_views(p->num_views, p->offs_b, p->uv_b, p->xyz_b);
-}
 
 // the two models of a joint call as compile-time shared counts
 template <typename F>
@@ -2466,132 +2522,54 @@ int dispatch_joint(int model_a, int model_b, F&& f) {
     });
 }
 
-// Device side of one joint call (StereoRun's shape): the problem, the two buffer sets the loop alternates between, the state.
-struct JointRun {
-    struct Cam {
-        DevBuf<int64_t> offs;
-        DevBuf<double2> uv;
-        DevBuf<double> xyz;
-        JointCam view() const { return JointCam{offs.p, uv.p, xyz.p}; }
-    };
-    Cam a, b;
-    DevBuf<double> Pj[2], rec[2], partA[2], tot, partC, delta, trace;
-    DevBuf<JointState> st;
-    int* done_host = nullptr;     // pinned: the decide / solve kernels set it when the loop is over
-    int64_t M = 0;
-    int nwgA = 0, nwgC = 0, model_a = 0, model_b = 0, S = 0, ntot = 0, nschur = 0;
-    JointBufs bufs{};
-    ~JointRun() { if (done_host) (void)hipHostFree(done_host); }
-
-    static int upload_cam(Cam& c, int64_t M, const int64_t* offs, const double* uv, const double* xyz) {
-        const int64_t n = offs[M];
-        HIP_TRY(c.offs.alloc((size_t)M + 1));
-        HIP_TRY(c.uv.alloc((size_t)std::max<int64_t>(n, 1)));
-        HIP_TRY(c.xyz.alloc((size_t)std::max<int64_t>(n, 1) * 3));
-        HIP_TRY(hipMemcpy(c.offs.p, offs, ((size_t)M + 1) * 8, hipMemcpyHostToDevice));
-        if (n) HIP_TRY(hipMemcpy(c.uv.p, uv, (size_t)n * 16, hipMemcpyHostToDevice));
-        if (n) HIP_TRY(hipMemcpy(c.xyz.p, xyz, (size_t)n * 24, hipMemcpyHostToDevice));
+int joint_evaluate(const StereoRun& r) {
+    const StereoCam ca = r.a.view(), cb = r.b.view();
+    const StereoBufs bf = r.bufs;
+    const unsigned grid = (unsigned)r.nwgA;
+    const int nwg = r.nwgA;
+    return dispatch_joint(r.model_a, r.model_b, [&](auto fa, auto fb) -> int {
+        constexpr int MA = decltype(fa)::MODEL, MB = decltype(fb)::MODEL;
+        hipLaunchKernelGGL((stereo_joint_blocks_kernel<MA, MB>), dim3(grid), dim3(64 * kJWaves), 0, 0, ca, cb, bf);
+        LAUNCHED(kNoHandle, "stereo_joint_blocks_kernel");
+        hipLaunchKernelGGL((stereo_joint_decide_kernel<ModelTraits<MA>::L, ModelTraits<MB>::L>), dim3(1), dim3(256), 0, 0,
+                           bf, nwg);
+        LAUNCHED(kNoHandle, "stereo_joint_decide_kernel");
         return CALIB_OK;
-    }
+    });
+}
 
-    // the start point goes into buffer 0, which the bootstrap round evaluates as its candidate (cur = 1)
-    int begin(const calib_stereo_problem_t* p, const double* Pj0, uint64_t fixed_mask, int max_iters, double lam,
-              double lam_min, double lam_max, double err_min, bool want_trace, bool want_notify) {
-        M = p->num_views; model_a = p->model_a; model_b = p->model_b;
-        S = joint_shared(p);
-        nwgA = (int)((M + kJWaves - 1) / kJWaves);
-        nwgC = (int)((M + 15) / 16);
-        dispatch_joint(model_a, model_b, [&](auto fa, auto fb) -> int {
-            using Y = JointLayout<ModelTraits<decltype(fa)::MODEL>::L, ModelTraits<decltype(fb)::MODEL>::L>;
-            ntot = Y::kTot; nschur = Y::kSchur;
-            return CALIB_OK;
-        });
-        const size_t K = (size_t)S + 6 * (size_t)M;
-        int rc = upload_cam(a, M, p->offs_a, p->uv_a, p->xyz_a);
-        if (rc) return rc;
-        rc = upload_cam(b, M, p->offs_b, p->uv_b, p->xyz_b);
-        if (rc) return rc;
-        for (int s = 0; s < 2; ++s) {
-            HIP_TRY(Pj[s].alloc(K));
-            HIP_TRY(rec[s].alloc((size_t)M * kJRecord));
-            HIP_TRY(partA[s].alloc((size_t)nwgA * ntot));
-        }
-        HIP_TRY(tot.alloc(2 * (size_t)ntot));
-        HIP_TRY(partC.alloc((size_t)nwgC * nschur));
-        HIP_TRY(delta.alloc(K));
-        HIP_TRY(st.alloc(1));
-        HIP_TRY(hipMemcpy(Pj[0].p, Pj0, K * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(Pj[1].p, Pj0, K * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemset(tot.p, 0, 2 * (size_t)ntot * 8));
-        if (want_trace) {
-            HIP_TRY(trace.alloc((size_t)max_iters * (CALIB_TRACE_HEADER + S)));
-            HIP_TRY(hipMemset(trace.p, 0, (size_t)max_iters * (CALIB_TRACE_HEADER + S) * 8));
-        }
-        JointState s{};
-        s.lam = lam; s.lam_min = lam_min; s.lam_max = lam_max; s.err_min = err_min;
-        s.err_cur = s.last_err = std::nan("");
-        s.fixed = fixed_mask;
-        s.cur = 1; s.max_iters = max_iters;
-        if (want_notify) {
-            void* hp = nullptr; void* dp = nullptr;
-            if (hipHostMalloc(&hp, sizeof(int), hipHostMallocMapped) == hipSuccess) {
-                done_host = static_cast<int*>(hp);
-                *done_host = 0;
-                if (hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) s.notify = static_cast<int*>(dp);
-            }
-            (void)hipGetLastError();
-        }
-        HIP_TRY(hipMemcpy(st.p, &s, sizeof s, hipMemcpyHostToDevice));
-        bufs = JointBufs{{Pj[0].p, Pj[1].p}, {rec[0].p, rec[1].p}, {partA[0].p, partA[1].p}, {tot.p, tot.p + ntot},
-                         partC.p, delta.p, trace.p, st.p, M};
+int joint_step(const StereoRun& r) {
+    const StereoCam ca = r.a.view(), cb = r.b.view();
+    const StereoBufs bf = r.bufs;
+    const int nwg = r.nwgC;
+    const unsigned gridB = (unsigned)((r.M + 63) / 64);
+    return dispatch_joint(r.model_a, r.model_b, [&](auto fa, auto fb) -> int {
+        constexpr int LA = ModelTraits<decltype(fa)::MODEL>::L, LB = ModelTraits<decltype(fb)::MODEL>::L;
+        using Y = JointLayout<LA, LB>;
+        hipLaunchKernelGGL((stereo_joint_schur_kernel<LA, LB>), dim3((unsigned)nwg), dim3(256), 0, 0, ca, cb, bf);
+        LAUNCHED(kNoHandle, "stereo_joint_schur_kernel");
+        hipLaunchKernelGGL((stereo_joint_solve_kernel<LA, LB>), dim3(1), dim3(256), 0, 0, bf, nwg);
+        LAUNCHED(kNoHandle, "stereo_joint_solve_kernel");
+        hipLaunchKernelGGL((stereo_backsub_kernel<Y, Y::S>), dim3(gridB), dim3(64), 0, 0, bf);
+        LAUNCHED(kNoHandle, "stereo_joint_backsub_kernel");
         return CALIB_OK;
-    }
-
-    // blocks at the candidate, then its totals and the decision
-    int evaluate() {
-        const JointCam ca = a.view(), cb = b.view();
-        const JointBufs bf = bufs;
-        const unsigned grid = (unsigned)nwgA;
-        const int nwg = nwgA;
-        return dispatch_joint(model_a, model_b, [&](auto fa, auto fb) -> int {
-            constexpr int MA = decltype(fa)::MODEL, MB = decltype(fb)::MODEL;
-            hipLaunchKernelGGL((stereo_joint_blocks_kernel<MA, MB>), dim3(grid), dim3(64 * kJWaves), 0, 0, ca, cb, bf);
-            LAUNCHED(kNoHandle, "stereo_joint_blocks_kernel");
-            hipLaunchKernelGGL((stereo_joint_decide_kernel<ModelTraits<MA>::L, ModelTraits<MB>::L>), dim3(1), dim3(256), 0, 0,
-                               bf, nwg);
-            LAUNCHED(kNoHandle, "stereo_joint_decide_kernel");
-            return CALIB_OK;
-        });
-    }
-
-    // the step at the accepted point: Schur complement, shared solve, back-substitution into the next candidate
-    int step() {
-        const JointCam ca = a.view(), cb = b.view();
-        const JointBufs bf = bufs;
-        const int nwg = nwgC;
-        const unsigned gridB = (unsigned)((M + 63) / 64);
-        return dispatch_joint(model_a, model_b, [&](auto fa, auto fb) -> int {
-            constexpr int LA = ModelTraits<decltype(fa)::MODEL>::L, LB = ModelTraits<decltype(fb)::MODEL>::L;
-            hipLaunchKernelGGL((stereo_joint_schur_kernel<LA, LB>), dim3((unsigned)nwg), dim3(256), 0, 0, ca, cb, bf);
-            LAUNCHED(kNoHandle, "stereo_joint_schur_kernel");
-            hipLaunchKernelGGL((stereo_joint_solve_kernel<LA, LB>), dim3(1), dim3(256), 0, 0, bf, nwg);
-            LAUNCHED(kNoHandle, "stereo_joint_solve_kernel");
-            hipLaunchKernelGGL((stereo_joint_backsub_kernel<LA, LB>), dim3(gridB), dim3(64), 0, 0, bf);
-            LAUNCHED(kNoHandle, "stereo_joint_backsub_kernel");
-            return CALIB_OK;
-        });
-    }
-
-    int state(JointState& s) {
-        HIP_TRY(hipMemcpy(&s, st.p, sizeof s, hipMemcpyDeviceToHost));
-        return CALIB_OK;
-    }
-};
+    });
+}
 
 int stereo_joint_singular() {
     return fail(CALIB_E_SINGULAR, "joint stereo normal equations singular: a view with fewer than three points in total, or "
                                   "a pivot of a view block or of the shared system that is not positive (a free parameter "
                                   "that no point constrains)");
+}
+
+StereoSolver joint_solver(int model_a, int model_b) {
+    StereoSolver sv{};
+    dispatch_joint(model_a, model_b, [&](auto fa, auto fb) -> int {
+        using Y = JointLayout<ModelTraits<decltype(fa)::MODEL>::L, ModelTraits<decltype(fb)::MODEL>::L>;
+        sv = StereoSolver{Y::S, kJRecord, Y::kTot, Y::kSchur, kJWaves, joint_evaluate, joint_step, stereo_joint_singular};
+        return CALIB_OK;
+    });
+    return sv;
 }
 
 }  // namespace
@@ -2600,19 +2578,11 @@ extern "C" {
 
 int calib_stereo_joint_normal_eq(const calib_stereo_problem_t* problem, const double* Pj, double* out_B, double* out_E,
                                  double* out_V, double* out_g, double* out_sse_ab, int device_id) {
-    int rc = check_stereo_joint(problem, Pj, 0);
+    StereoRun run;
+    std::vector<double> rec, tot;
+    const int rc = stereo_blocks(run, true, problem, Pj, device_id, rec, tot);
     if (rc) return rc;
-    rc = use_device(device_id);
-    if (rc) return rc;
-    JointRun run;
-    rc = run.begin(problem, Pj, 0, 1, 0.0, 0.0, 0.0, 0.0, false, false);
-    if (rc) return rc;
-    rc = run.evaluate();
-    if (rc) return rc;
-    const size_t M = (size_t)problem->num_views, S = (size_t)run.S;
-    std::vector<double> rec(M * kJRecord), tot((size_t)run.ntot);
-    HIP_TRY(hipMemcpy(rec.data(), run.rec[0].p, rec.size() * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(tot.data(), run.tot.p, tot.size() * 8, hipMemcpyDeviceToHost));
+    const size_t M = (size_t)problem->num_views, S = (size_t)run.sv.S;
     return dispatch_joint(problem->model_a, problem->model_b, [&](auto fa, auto fb) -> int {
         using Y = JointLayout<ModelTraits<decltype(fa)::MODEL>::L, ModelTraits<decltype(fb)::MODEL>::L>;
         if (out_B)
@@ -2625,9 +2595,7 @@ int calib_stereo_joint_normal_eq(const calib_stereo_problem_t* problem, const do
         if (out_sse_ab) { out_sse_ab[0] = tot[Y::kErr]; out_sse_ab[1] = tot[Y::kErr + 1]; }
         for (size_t v = 0; v < M; ++v) {
             const double* r = rec.data() + v * kJRecord;
-            if (out_V)
-                for (int i = 0; i < 6; ++i)
-                    for (int j = 0; j <= i; ++j) out_V[v * 36 + i * 6 + j] = out_V[v * 36 + j * 6 + i] = r[Y::kV + i * (i + 1) / 2 + j];
+            if (out_V) sym6(r + Y::kV, out_V + v * 36);
             if (out_E) std::copy(r + Y::kE, r + Y::kE + 6 * Y::S, out_E + v * 6 * S);
             if (out_g) std::copy(r + Y::kGv, r + Y::kGv + 6, out_g + S + v * 6);
         }
@@ -2637,64 +2605,14 @@ int calib_stereo_joint_normal_eq(const calib_stereo_problem_t* problem, const do
 
 int calib_stereo_joint_step_delta(const calib_stereo_problem_t* problem, const double* Pj, uint64_t fixed_mask,
                                   double lambda, double* out_delta, int device_id) {
-    int rc = check_stereo_joint(problem, Pj, fixed_mask);
-    if (rc) return rc;
-    rc = use_device(device_id);
-    if (rc) return rc;
-    JointRun run;
-    rc = run.begin(problem, Pj, fixed_mask, 1, lambda, 0.0, 0.0, 0.0, false, false);
-    if (rc) return rc;
-    rc = run.evaluate();
-    if (rc) return rc;
-    rc = run.step();
-    if (rc) return rc;
-    JointState s;
-    rc = run.state(s);
-    if (rc) return rc;
-    if (s.error) return stereo_joint_singular();
-    if (out_delta)
-        HIP_TRY(hipMemcpy(out_delta, run.delta.p, ((size_t)run.S + 6 * (size_t)problem->num_views) * 8, hipMemcpyDeviceToHost));
-    return CALIB_OK;
+    return stereo_step_delta(true, problem, Pj, fixed_mask, lambda, out_delta, device_id);
 }
 
 int calib_refine_stereo_joint(const calib_stereo_problem_t* problem, double* Pj_inout, uint64_t fixed_mask, int max_iters,
                               double lam_init, double lam_min, double lam_max, double err_min, double* out_sse,
                               double* out_sse_ab, int* out_iters, double* out_trace, int device_id) {
-    if (max_iters <= 0) return fail(CALIB_E_INVALID, "max_iters must be >= 1");
-    int rc = check_stereo_joint(problem, Pj_inout, fixed_mask);
-    if (rc) return rc;
-    rc = use_device(device_id);
-    if (rc) return rc;
-    JointRun run;
-    rc = run.begin(problem, Pj_inout, fixed_mask, max_iters, lam_init, lam_min, lam_max, err_min, out_trace != nullptr, true);
-    if (rc) return rc;
-    // as calib_refine_stereo: round 0 evaluates the start point, round r >= 1 decides iteration r - 1; the rounds are
-    // enqueued back to back and only the done word in pinned memory is looked at
-    JointState s;
-    for (int r = 0; r <= max_iters; ++r) {
-        rc = run.evaluate();
-        if (rc) return rc;
-        rc = run.step();
-        if (rc) return rc;
-        if (run.done_host) {
-            if (*static_cast<volatile int*>(run.done_host)) break;
-        } else if ((r + 1) % 8 == 0) {
-            rc = run.state(s);
-            if (rc) return rc;
-            if (s.done) break;
-        }
-    }
-    rc = run.state(s);
-    if (rc) return rc;
-    if (s.error) return stereo_joint_singular();
-    const size_t K = (size_t)run.S + 6 * (size_t)problem->num_views;
-    const size_t W = (size_t)(CALIB_TRACE_HEADER + run.S);
-    HIP_TRY(hipMemcpy(Pj_inout, run.Pj[s.cur].p, K * 8, hipMemcpyDeviceToHost));
-    if (out_sse) *out_sse = s.last_err;
-    if (out_iters) *out_iters = s.iters;
-    if (out_sse_ab) HIP_TRY(hipMemcpy(out_sse_ab, run.tot.p + (size_t)s.cur * run.ntot + (run.ntot - 2), 16, hipMemcpyDeviceToHost));
-    if (out_trace && s.iters > 0) HIP_TRY(hipMemcpy(out_trace, run.trace.p, (size_t)s.iters * W * 8, hipMemcpyDeviceToHost));
-    return CALIB_OK;
+    return stereo_refine(true, problem, Pj_inout, fixed_mask, max_iters, lam_init, lam_min, lam_max, err_min, out_sse,
+                         out_sse_ab, out_iters, out_trace, device_id);
 }
 
 }  // extern "C"

@@ -18,11 +18,12 @@
 //                          row c of E_i V_i^-1 E_i^T and of E_i V_i^-1 g_i; summed over the workgroup -> one partial
 //   stereo_rig_kernel      one workgroup: the partials in one fixed order, S = B + lam diag B - sum, Cholesky, delta_rig
 //   stereo_backsub_kernel  one lane per view: delta_i = (V_i + lam diag V_i)^-1 (g_i - E_i^T delta_rig), next candidate
-// Every kernel returns at once when the state says the loop is over, so the host may run ahead.
-// All five are templates (the four that need no model take the width they sum or launch with): a template is emitted
-// where it is first launched, at the end of the module, so the module's other kernels keep their place and labels.
+//                          (stereo_loop.hpp's, on this file's record with S = 6)
+// The state, the decision, the end of the loop and the sum of the partials are stereo_loop.hpp's, shared with the joint
+// solver. All kernels are templates (those that need no model take the width they sum or launch with): a template is
+// emitted where it is first launched, at the end of the module, so the module's other kernels keep their place and labels.
 #pragma once
-#include "kernels.hpp"
+#include "stereo_loop.hpp"
 
 namespace calib {
 
@@ -31,31 +32,10 @@ constexpr int kStV = 0, kStE = 21, kStB = 57, kStGr = 78, kStGv = 84, kStErr = 9
 constexpr int kStRecord = 96;
 constexpr int kStTot = 29;            // what is summed over the views at once: B (21), g_rig (6), sse_a, sse_b = record [kStB, kStAcc) minus g_view
 constexpr int kStSchur = 43;          // rows c < 6 of (E V^-1 E^T | E V^-1 g) (42), number of failed views
-constexpr int kStTrace = 5 + 6;       // CALIB_TRACE_HEADER + the rig
 
-struct StereoCam {
-    const int64_t* offs; const double2* uv; const double* xyz; const double* shared;
-};
-
-struct StereoState {
-    double lam, err_cur, last_err, lam_min, lam_max, err_min;
-    double drig[6];
-    int cur;        // index of the buffers holding the accepted point; the candidate lives in cur ^ 1
-    int round;      // 0: the next decide is the bootstrap (the candidate IS the start point)
-    int iters, max_iters, done, error;
-    int* notify;    // host-visible word set when the loop is over (or null)
-};
-
-struct StereoBufs {
-    double* Ps[2];        // 6 + 6 M
-    double* rec[2];       // M * kStRecord
-    double* partA[2];     // workgroups of stereo_blocks_kernel * kStTot
-    double* tot[2];       // kStTot
-    double* partC;        // workgroups of stereo_schur_kernel * kStSchur
-    double* delta;        // 6 + 6 M: the last step
-    double* trace;        // max_iters * kStTrace, or null
-    StereoState* st;
-    int64_t M;
+// the record as stereo_backsub_kernel reads it
+struct StereoRecord {
+    static constexpr int kV = kStV, kE = kStE, kGv = kStGv, kStride = kStRecord;
 };
 
 // slot of record entry j in [kStB, kStAcc) among the kStTot summed ones, or -1 (g_view is per view)
@@ -63,42 +43,15 @@ __device__ __forceinline__ constexpr int stTotSlot(int j) {
     return j < kStB ? -1 : j < kStGv ? j - kStB : j < kStErr ? -1 : j - kStErr + 27;
 }
 
-// Entry j < N of the nwg workgroup partials (rows of N doubles), summed in one fixed order by 256 lanes: lane (seg, j)
-// adds its quarter of the rows in index order -- eight loads in flight at a time, a chain of dependent loads is what a
-// one-wave sum of 625 rows spent 150 us on -- and the four quarters are added in order. Every lane gets entry
-// (tid & 63)'s total; sh keeps the quarters (stereo_total reads any entry's total from it afterwards).
-__device__ __forceinline__ double stereo_total(const double (&sh)[4][64], int j) {
-    return ((sh[0][j] + sh[1][j]) + sh[2][j]) + sh[3][j];
-}
-template <int N>
-__device__ __forceinline__ double stereo_sum_partials(const double* __restrict__ p, int nwg, double (&sh)[4][64]) {
-    const int seg = threadIdx.x >> 6, j = threadIdx.x & 63;
-    const int q = (nwg + 3) / 4, w1 = min(nwg, (seg + 1) * q);
-    double s = 0.0;
-    if (j < N) {
-        int w = seg * q;
-        for (; w + 8 <= w1; w += 8) {
-            double v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = p[(int64_t)(w + u) * N + j];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += v[u];
-        }
-        for (; w < w1; ++w) s += p[(int64_t)w * N + j];
-    }
-    sh[seg][j] = s;
-    __syncthreads();
-    return stereo_total(sh, j);
-}
-
 template <int MODEL_A, int MODEL_B>
-__global__ __launch_bounds__(256) void stereo_blocks_kernel(StereoCam ca, StereoCam cb, StereoBufs bf) {
+__global__ __launch_bounds__(256) void stereo_blocks_kernel(StereoCam ca, const double* shared_a, StereoCam cb,
+                                                            const double* shared_b, StereoBufs bf) {
     constexpr int LA = ModelTraits<MODEL_A>::L, CA = ModelTraits<MODEL_A>::C;
     constexpr int LB = ModelTraits<MODEL_B>::L, CB = ModelTraits<MODEL_B>::C;
     __shared__ double sh[16][kStTot];
     if (bf.st->done) return;
     const int cand = bf.st->cur ^ 1;
-    const double* __restrict__ Ps = bf.Ps[cand];
+    const double* __restrict__ Ps = bf.P[cand];
     const int tid = threadIdx.x, i = tid & 15, grp = tid >> 4;
     const int64_t view = (int64_t)blockIdx.x * 16 + grp;
     double acc[kStAcc];
@@ -112,7 +65,7 @@ __global__ __launch_bounds__(256) void stereo_blocks_kernel(StereoCam ca, Stereo
         pose_view_constants(rg, vr);
         {
             Shared<MODEL_A, double> sp;
-            sp.load(ca.shared);
+            sp.load(shared_a);
             const int64_t p0 = ca.offs[view];
             const int n = (int)(ca.offs[view + 1] - p0);
             for (int q = i; q < n; q += 16) {
@@ -133,7 +86,7 @@ __global__ __launch_bounds__(256) void stereo_blocks_kernel(StereoCam ca, Stereo
         }
         {
             Shared<MODEL_B, double> sp;
-            sp.load(cb.shared);
+            sp.load(shared_b);
             const int64_t p0 = cb.offs[view];
             const int n = (int)(cb.offs[view + 1] - p0);
             for (int q = i; q < n; q += 16) {
@@ -203,43 +156,16 @@ __global__ __launch_bounds__(256) void stereo_blocks_kernel(StereoCam ca, Stereo
     }
 }
 
-// The candidate's totals, then the decision of src/calibrate.py:161-168: accept iff err(P + delta) < err(P) strictly
-// (NaN rejects), lambda / 10 or * 10, stop when lambda leaves (lam_min, lam_max) or err(P) < err_min or max_iters ran.
+// The candidate's totals, then the decision (stereo_decide).
 template <int NTOT>
 __global__ __launch_bounds__(256) void stereo_decide_kernel(StereoBufs bf, int nwg) {
     static_assert(NTOT == kStTot && NTOT <= 64, "one lane per summed entry");
     __shared__ double sh[4][64];
-    StereoState* st = bf.st;
-    if (st->done) return;
-    const int cand = st->cur ^ 1, tid = threadIdx.x;
-    const double total = stereo_sum_partials<NTOT>(bf.partA[cand], nwg, sh);
-    if (tid < NTOT) bf.tot[cand][tid] = total;
-    if (tid != 0) return;
-    const double err1 = stereo_total(sh, 27) + stereo_total(sh, 28);
-    if (st->round == 0) {
-        st->err_cur = err1;
-        st->cur = cand;
-        st->round = 1;
-        return;
-    }
-    const int it = st->iters;
-    const double err0 = st->err_cur, lam = st->lam;
-    const bool accepted = err1 < err0;
-    if (bf.trace) {
-        double* row = bf.trace + (int64_t)it * kStTrace;
-        row[0] = it; row[1] = err0; row[2] = err1; row[3] = lam; row[4] = accepted ? 1.0 : 0.0;
-        for (int j = 0; j < 6; ++j) row[5 + j] = bf.Ps[cand ^ 1][j];
-    }
-    const double lam1 = accepted ? lam / 10 : lam * 10;
-    if (accepted) { st->cur = cand; st->err_cur = err1; }
-    st->lam = lam1;
-    st->last_err = err0;
-    st->iters = it + 1;
-    st->round = st->round + 1;
-    if (!(st->lam_min < lam1 && lam1 < st->lam_max) || err0 < st->err_min || it + 1 >= st->max_iters) {
-        st->done = 1;
-        if (st->notify) __hip_atomic_store(st->notify, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    if (bf.st->done) return;
+    const int cand = bf.st->cur ^ 1, tid = threadIdx.x;
+    joint_sum_partials<NTOT>(bf.partA[cand], nwg, sh);
+    if (tid < NTOT) bf.tot[cand][tid] = joint_total(sh, tid);
+    if (tid == 0) stereo_decide<6>(bf, cand, joint_total(sh, 27) + joint_total(sh, 28));
 }
 
 // Per view: Lc Lc^T = V + lam diag V; lane c < 6 substitutes row c of E, lane 6 the view gradient; row c of
@@ -304,8 +230,8 @@ __global__ __launch_bounds__(256) void stereo_rig_kernel(StereoBufs bf, int nwg)
     StereoState* st = bf.st;
     if (st->done) return;
     const int tid = threadIdx.x;
-    const double total = stereo_sum_partials<NSUM>(bf.partC, nwg, sh4);
-    if (tid < NSUM) sh[tid] = total;
+    joint_sum_partials<NSUM>(bf.partC, nwg, sh4);
+    if (tid < NSUM) sh[tid] = joint_total(sh4, tid);
     __syncthreads();
     if (tid != 0) return;
     bool ok = !(sh[42] != 0.0);
@@ -324,50 +250,11 @@ __global__ __launch_bounds__(256) void stereo_rig_kernel(StereoBufs bf, int nwg)
     ok = eliminate(S, s, 0.0, invd, z) && ok;
     backward6(S, invd, z, d);
     if (!ok) {
-        st->error = -3;
-        st->done = 1;
-        if (st->notify) __hip_atomic_store(st->notify, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        stereo_stop(st, -3);
         return;
     }
 #pragma unroll
-    for (int a = 0; a < 6; ++a) st->drig[a] = d[a];
-}
-
-// delta_i = (V_i + lam diag V_i)^-1 (g_i - E_i^T delta_rig); the next candidate = accepted point + delta
-template <int WIDTH>
-__global__ __launch_bounds__(WIDTH) void stereo_backsub_kernel(StereoBufs bf) {
-    const StereoState* st = bf.st;
-    if (st->done) return;
-    const int64_t view = (int64_t)blockIdx.x * WIDTH + threadIdx.x;
-    if (view >= bf.M) return;
-    const int cur = st->cur;
-    const double* __restrict__ rec = bf.rec[cur] + view * kStRecord;
-    const double* __restrict__ Pc = bf.Ps[cur];
-    double* __restrict__ Pn = bf.Ps[cur ^ 1];
-    double V[21], b[6], invd[6], z[6], d[6], dr[6];
-#pragma unroll
-    for (int a = 0; a < 6; ++a) dr[a] = st->drig[a];
-#pragma unroll
-    for (int j = 0; j < 21; ++j) V[j] = rec[kStV + j];
-#pragma unroll
-    for (int m = 0; m < 6; ++m) {
-        double s = rec[kStGv + m];
-#pragma unroll
-        for (int a = 0; a < 6; ++a) s -= rec[kStE + a * 6 + m] * dr[a];
-        b[m] = s;
-    }
-    eliminate(V, b, st->lam, invd, z);
-    backward6(V, invd, z, d);
-#pragma unroll
-    for (int m = 0; m < 6; ++m) {
-        const int64_t o = 6 + 6 * view + m;
-        bf.delta[o] = d[m];
-        Pn[o] = Pc[o] + d[m];
-    }
-    if (view == 0) {
-#pragma unroll
-        for (int a = 0; a < 6; ++a) { bf.delta[a] = dr[a]; Pn[a] = Pc[a] + dr[a]; }
-    }
+    for (int a = 0; a < 6; ++a) st->dsh[a] = d[a];
 }
 
 }  // namespace calib

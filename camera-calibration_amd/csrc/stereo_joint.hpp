@@ -17,9 +17,11 @@
 //                                eliminate(); the workgroup's 16 views' Z^T Z and Z^T z_g summed in view order -> partial
 //   stereo_joint_solve_kernel    one workgroup: partials in one order, B + lam diag B - sum, the fixed mask, Cholesky of
 //                                the S x S system in one wave's registers, substitution -> delta_shared
-//   stereo_joint_backsub_kernel  one lane per view: delta_i, the next candidate, the step
-// Every kernel returns at once when the state says the loop is over, so the host may run ahead. All five are templates:
-// they are emitted where they are first launched, at the end of the module.
+//   stereo_backsub_kernel        one lane per view: delta_i, the next candidate, the step (stereo_loop.hpp's, on
+//                                JointLayout's record with this S)
+// The buffers, the state, the decision, the end of the loop and the sum of the partials are stereo_loop.hpp's, shared
+// with the rig-only solver. All kernels are templates: they are emitted where they are first launched, at the end of
+// the module.
 //
 // Tile maps (C/D layout of the fp64 MFMA: lane (k, c) = (lane >> 4, lane & 15) holds rows k + 4 reg of column c):
 //   camera a   columns [view 6 | shared_a | pad]                     Ta  = J^T J
@@ -37,7 +39,6 @@ constexpr int kJRows = 32;                         // points transposed per pass
 constexpr int kJSlab = kJRows * kJRowChunks;       // chunks (double2) per wave: 16.5 KiB
 constexpr int kJWaves = 4;                         // views per workgroup
 constexpr int kJRecord = 184;                      // doubles per view record (21 + 6 * 26 + 6 = 183 used at most)
-constexpr int kJMaxS = 26;
 // a wave's parked results (doubles, in its dead slab): four 16 x 16 tiles, three J^T r vectors, two errors
 constexpr int kJTa = 0, kJT00 = 256, kJT10 = 512, kJT11 = 768, kJGa = 1024, kJGb0 = 1040, kJGb1 = 1056, kJErr = 1072;
 static_assert(kJErr + 2 <= 2 * kJSlab, "the parked results must fit the wave's slab");
@@ -46,7 +47,7 @@ template <int LA, int LB>
 struct JointLayout {
     static constexpr int S = LA + LB + 6, LR = LB + 6;
     // view record: V lower triangle, E row-major (shared row, view column), g_view
-    static constexpr int kV = 0, kE = 21, kGv = 21 + 6 * S, kRec = kGv + 6;
+    static constexpr int kV = 0, kE = 21, kGv = 21 + 6 * S, kRec = kGv + 6, kStride = kJRecord;
     // what is summed over the views: lower triangles of B_aa and of B over (b, rig), g_shared, sse_a, sse_b
     static constexpr int kBa = 0, kBr = LA * (LA + 1) / 2, kG = kBr + LR * (LR + 1) / 2, kErr = kG + S, kTot = kErr + 2;
     // Schur partial: lower triangle of sum Z^T Z (S x S), sum E V^-1 g (S), number of failed views
@@ -72,58 +73,6 @@ __device__ __forceinline__ double2 live_or_zero(bool live, double2 v) {
     o.x = live ? v.x : 0.0;
     o.y = live ? v.y : 0.0;
     return o;
-}
-
-struct JointCam {
-    const int64_t* offs; const double2* uv; const double* xyz;
-};
-
-struct JointState {
-    double lam, err_cur, last_err, lam_min, lam_max, err_min;
-    double dsh[kJMaxS];             // the shared part of the step
-    unsigned long long fixed;       // bit s: shared unknown s is held fixed
-    int cur;        // index of the buffers holding the accepted point; the candidate lives in cur ^ 1
-    int round;      // 0: the next decide is the bootstrap (the candidate IS the start point)
-    int iters, max_iters, done, error;
-    int* notify;    // host-visible word set when the loop is over (or null)
-};
-
-struct JointBufs {
-    double* Pj[2];        // S + 6 M
-    double* rec[2];       // M * kJRecord
-    double* partA[2];     // workgroups of the blocks kernel * kTot
-    double* tot[2];       // kTot
-    double* partC;        // workgroups of the schur kernel * kSchur
-    double* delta;        // S + 6 M: the last step
-    double* trace;        // max_iters * (5 + S), or null
-    JointState* st;
-    int64_t M;
-};
-
-// Entry j < N (any N <= NP) of the nwg workgroup partials, summed in one fixed order by 256 lanes: stereo_sum_partials'
-// quarters, lane (seg, j) taking entries j, j + 64, ..; total j = ((q0 + q1) + q2) + q3 from sh after the barrier.
-template <int N, int NP>
-__device__ __forceinline__ void joint_sum_partials(const double* __restrict__ p, int nwg, double (&sh)[4][NP]) {
-    const int seg = threadIdx.x >> 6;
-    const int q = (nwg + 3) / 4, w0 = seg * q, w1 = min(nwg, (seg + 1) * q);
-    for (int j = threadIdx.x & 63; j < N; j += 64) {
-        double s = 0.0;
-        int w = w0;
-        for (; w + 8 <= w1; w += 8) {
-            double v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = p[(int64_t)(w + u) * N + j];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += v[u];
-        }
-        for (; w < w1; ++w) s += p[(int64_t)w * N + j];
-        sh[seg][j] = s;
-    }
-    __syncthreads();
-}
-template <int NP>
-__device__ __forceinline__ double joint_total(const double (&sh)[4][NP], int j) {
-    return ((sh[0][j] + sh[1][j]) + sh[2][j]) + sh[3][j];
 }
 
 // entry j of a view's record / entry e of the workgroup partial, from one wave's parked results
@@ -161,14 +110,14 @@ __device__ __forceinline__ double joint_partial_entry(const double* __restrict__
 }
 
 template <int MODEL_A, int MODEL_B>
-__global__ __launch_bounds__(64 * kJWaves) void stereo_joint_blocks_kernel(JointCam ca, JointCam cb, JointBufs bf) {
+__global__ __launch_bounds__(64 * kJWaves) void stereo_joint_blocks_kernel(StereoCam ca, StereoCam cb, StereoBufs bf) {
     constexpr int LA = ModelTraits<MODEL_A>::L, CA = ModelTraits<MODEL_A>::C;
     constexpr int LB = ModelTraits<MODEL_B>::L, CB = ModelTraits<MODEL_B>::C;
     using Y = JointLayout<LA, LB>;
     __shared__ __attribute__((aligned(16))) double2 smem[kJWaves * kJSlab];
     if (bf.st->done) return;
     const int cand = bf.st->cur ^ 1;
-    const double* __restrict__ Pj = bf.Pj[cand];
+    const double* __restrict__ Pj = bf.P[cand];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int k = lane >> 4, c = lane & 15;
     const int64_t view = (int64_t)blockIdx.x * kJWaves + wave;
@@ -252,6 +201,8 @@ __global__ __launch_bounds__(64 * kJWaves) void stereo_joint_blocks_kernel(Joint
                 double2 res;
                 res.x = live ? m.x - u : 0.0;
                 res.y = live ? m.y - v : 0.0;
+                // stereo_blocks_kernel's chain rule, written out here as there: moved into a function the two kernels
+                // share, the compiler contracts Jv[1] the other way round here (bits change) and reschedules that kernel
                 // G R_rig (2 x 3), G = d(uv)/dXb = the translation columns
                 double2 GR[3];
 #pragma unroll
@@ -342,54 +293,28 @@ __global__ __launch_bounds__(64 * kJWaves) void stereo_joint_blocks_kernel(Joint
     }
 }
 
-// The candidate's totals, then the decision of src/calibrate.py:161-168 (stereo_decide_kernel's, with S trace columns).
+// The candidate's totals, then the decision (stereo_decide, with S trace columns).
 template <int LA, int LB>
-__global__ __launch_bounds__(256) void stereo_joint_decide_kernel(JointBufs bf, int nwg) {
+__global__ __launch_bounds__(256) void stereo_joint_decide_kernel(StereoBufs bf, int nwg) {
     using Y = JointLayout<LA, LB>;
     __shared__ double sh[4][kJMaxTot + 1];
-    JointState* st = bf.st;
-    if (st->done) return;
-    const int cand = st->cur ^ 1, tid = threadIdx.x;
+    if (bf.st->done) return;
+    const int cand = bf.st->cur ^ 1, tid = threadIdx.x;
     joint_sum_partials<Y::kTot>(bf.partA[cand], nwg, sh);
     if (tid < Y::kTot) bf.tot[cand][tid] = joint_total(sh, tid);
-    if (tid != 0) return;
-    const double err1 = joint_total(sh, Y::kErr) + joint_total(sh, Y::kErr + 1);
-    if (st->round == 0) {
-        st->err_cur = err1;
-        st->cur = cand;
-        st->round = 1;
-        return;
-    }
-    const int it = st->iters;
-    const double err0 = st->err_cur, lam = st->lam;
-    const bool accepted = err1 < err0;
-    if (bf.trace) {
-        double* row = bf.trace + (int64_t)it * (5 + Y::S);
-        row[0] = it; row[1] = err0; row[2] = err1; row[3] = lam; row[4] = accepted ? 1.0 : 0.0;
-        for (int j = 0; j < Y::S; ++j) row[5 + j] = bf.Pj[cand ^ 1][j];
-    }
-    const double lam1 = accepted ? lam / 10 : lam * 10;
-    if (accepted) { st->cur = cand; st->err_cur = err1; }
-    st->lam = lam1;
-    st->last_err = err0;
-    st->iters = it + 1;
-    st->round = st->round + 1;
-    if (!(st->lam_min < lam1 && lam1 < st->lam_max) || err0 < st->err_min || it + 1 >= st->max_iters) {
-        st->done = 1;
-        if (st->notify) __hip_atomic_store(st->notify, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    if (tid == 0) stereo_decide<Y::S>(bf, cand, joint_total(sh, Y::kErr) + joint_total(sh, Y::kErr + 1));
 }
 
 // Per view: Lc Lc^T = V + lam diag V; lane i substitutes right-hand sides i and i + 16 of the S + 1 (rows of E, then the
 // view gradient) into the workgroup's LDS; then entry e of (Z^T Z | Z^T z_g) is summed over the 16 views in index order by
 // thread e, e + 256. A view with fewer than three points in total, or with a pivot that is not positive, counts as failed.
 template <int LA, int LB>
-__global__ __launch_bounds__(256) void stereo_joint_schur_kernel(JointCam ca, JointCam cb, JointBufs bf) {
+__global__ __launch_bounds__(256) void stereo_joint_schur_kernel(StereoCam ca, StereoCam cb, StereoBufs bf) {
     using Y = JointLayout<LA, LB>;
     constexpr int S = Y::S, ZS = (S + 1) * 6;
     __shared__ double zs[16][ZS];
     __shared__ double sfail[16];
-    const JointState* st = bf.st;
+    const StereoState* st = bf.st;
     if (st->done) return;
     const int tid = threadIdx.x, i = tid & 15, grp = tid >> 4;
     const int64_t view = (int64_t)blockIdx.x * 16 + grp;
@@ -446,12 +371,12 @@ __global__ __launch_bounds__(256) void stereo_joint_schur_kernel(JointCam ca, Jo
 // lane i holding row i, pivots and multipliers passed by v_readlane. A failed view or a pivot that is not positive ends
 // the loop with CALIB_E_SINGULAR (-3).
 template <int LA, int LB>
-__global__ __launch_bounds__(256) void stereo_joint_solve_kernel(JointBufs bf, int nwg) {
+__global__ __launch_bounds__(256) void stereo_joint_solve_kernel(StereoBufs bf, int nwg) {
     using Y = JointLayout<LA, LB>;
     constexpr int S = Y::S;
     __shared__ double sh[4][kJMaxSchur + 1];
     __shared__ double Lsh[S][S + 1];
-    JointState* st = bf.st;
+    StereoState* st = bf.st;
     if (st->done) return;
     const int tid = threadIdx.x;
     joint_sum_partials<Y::kSchur>(bf.partC, nwg, sh);
@@ -485,11 +410,7 @@ __global__ __launch_bounds__(256) void stereo_joint_solve_kernel(JointBufs bf, i
         for (int cI = j + 1; cI < S; ++cI) row[cI] -= lij * readlane_d(lij, cI);
     }
     if (!ok) {                                               // the same for every lane
-        if (tid == 0) {
-            st->error = -3;
-            st->done = 1;
-            if (st->notify) __hip_atomic_store(st->notify, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
+        if (tid == 0) stereo_stop(st, -3);
         return;
     }
     // forward: z_j = y_j / L_jj, y_i -= L_ij z_j (i > j); lane j keeps z_j
@@ -511,48 +432,6 @@ __global__ __launch_bounds__(256) void stereo_joint_solve_kernel(JointBufs bf, i
         const double xj = readlane_d(t, j) * invs[j];
         if (tid < j) t -= Lsh[j][tid] * xj;
         if (tid == 0) st->dsh[j] = xj;
-    }
-}
-
-// delta_i = (V_i + lam diag V_i)^-1 (g_i - E_i^T delta_shared); the next candidate = accepted point + delta. A fixed
-// shared unknown is copied, not added to: its bits are kept (-0.0 + 0.0 is +0.0).
-template <int LA, int LB>
-__global__ __launch_bounds__(64) void stereo_joint_backsub_kernel(JointBufs bf) {
-    using Y = JointLayout<LA, LB>;
-    constexpr int S = Y::S;
-    const JointState* st = bf.st;
-    if (st->done) return;
-    const int64_t view = (int64_t)blockIdx.x * 64 + threadIdx.x;
-    if (view >= bf.M) return;
-    const int cur = st->cur;
-    const double* __restrict__ rec = bf.rec[cur] + view * kJRecord;
-    const double* __restrict__ Pc = bf.Pj[cur];
-    double* __restrict__ Pn = bf.Pj[cur ^ 1];
-    double V[21], b[6], invd[6], z[6], d[6];
-#pragma unroll
-    for (int j = 0; j < 21; ++j) V[j] = rec[Y::kV + j];
-#pragma unroll
-    for (int m = 0; m < 6; ++m) b[m] = rec[Y::kGv + m];
-    for (int s = 0; s < S; ++s) {
-        const double ds = st->dsh[s];
-#pragma unroll
-        for (int m = 0; m < 6; ++m) b[m] -= rec[Y::kE + s * 6 + m] * ds;
-    }
-    eliminate(V, b, st->lam, invd, z);
-    backward6(V, invd, z, d);
-#pragma unroll
-    for (int m = 0; m < 6; ++m) {
-        const int64_t o = S + 6 * view + m;
-        bf.delta[o] = d[m];
-        Pn[o] = Pc[o] + d[m];
-    }
-    if (view == 0) {
-        const unsigned long long fixed = st->fixed;
-        for (int s = 0; s < S; ++s) {
-            const double ds = st->dsh[s];
-            bf.delta[s] = ds;
-            Pn[s] = ((fixed >> s) & 1) ? Pc[s] : Pc[s] + ds;
-        }
     }
 }
 

@@ -119,7 +119,7 @@ def main():
         doc = json.load(open(args.merge))
         if args.trace:
             kern = traceMedians(args.trace)
-            joint = {n: v for n, v in kern.items() if n.startswith("stereo_joint_")}
+            joint = {n: v for n, v in kern.items() if n.startswith("stereo_joint_") or "JointLayout" in n}   # + the shared back-substitution
             rounds = max(v["dispatches"] for v in joint.values()) if joint else 0
             doc["kernel_trace"] = {"run": f"one calib_refine_stereo_joint call of {doc['joint']['iters'][0]} iterations "
                                           "under rocprofv3 --kernel-trace, a run of its own", "kernels": joint,
