@@ -5,7 +5,7 @@ src/jacobian.py, src/distortion.py). Import as ``camera_calibration_amd`` (the
 repo-root shim maps the hyphenated directory name onto that module name).
 """
 from . import (_native, calibrate, dataset, distortion, engine, fixed, jacobian, linearcalibrate, main,  # noqa: F401
-               mathutils, rectify, stereo, synthetic, uncertainty, undistort)
+               mathutils, rectify, rig, stereo, synthetic, uncertainty, undistort)
 from .calibrate import Calibrator, getSensorPoints  # noqa: F401
 from .distortion import FisheyeModel, RadialTangentialModel  # noqa: F401
 from .engine import RefineEngine  # noqa: F401
@@ -13,6 +13,7 @@ from .jacobian import HomographyJacobian, ProjectionJacobian, createJacRadTan  #
 from .main import calibrateCamera, calibrateCameraExtended, estimatePoses  # noqa: F401
 from .rectify import (StereoRectification, optimalNewCameraMatrix, rectifyRotations, stereoRectify,  # noqa: F401
                       triangulate)
+from .rig import RigCalibration, calibrateRig, rigCalibrate, rigStartPoints  # noqa: F401
 from .stereo import StereoCalibration, calibrateStereo, stereoCalibrate  # noqa: F401
 from .uncertainty import CalibrationUncertainty  # noqa: F401
 from .undistort import Undistorter, remap, undistortImage  # noqa: F401

@@ -36,6 +36,21 @@ class StereoProblem(ctypes.Structure):
 
 
 _stereo_p = ctypes.POINTER(StereoProblem)
+RIG_MAX_CAMERAS = 8
+
+
+class RigCamera(ctypes.Structure):
+    """calib_rig_camera_t"""
+    _fields_ = [("model", ctypes.c_int), ("offs", _c_int64_p), ("uv", _c_double_p), ("xyz", _c_double_p),
+                ("shared", _c_double_p)]
+
+
+class RigProblem(ctypes.Structure):
+    """calib_rig_problem_t"""
+    _fields_ = [("num_cameras", ctypes.c_int), ("num_views", ctypes.c_int64), ("cameras", ctypes.POINTER(RigCamera))]
+
+
+_rig_p = ctypes.POINTER(RigProblem)
 
 # name -> (restype, argtypes); must list every symbol include/calib_lm.h declares
 SIGNATURES = {
@@ -131,6 +146,12 @@ SIGNATURES = {
     "calib_refine_stereo_joint": (ctypes.c_int, [_stereo_p, _c_double_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_double,
                                                  ctypes.c_double, ctypes.c_double, ctypes.c_double, _c_double_p, _c_double_p,
                                                  _c_int_p, _c_double_p, ctypes.c_int]),
+    "calib_rig_normal_eq": (ctypes.c_int, [_rig_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+                                           _c_double_p, ctypes.c_int]),
+    "calib_rig_step_delta": (ctypes.c_int, [_rig_p, _c_double_p, ctypes.c_double, _c_double_p, ctypes.c_int]),
+    "calib_refine_rig": (ctypes.c_int, [_rig_p, _c_double_p, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                        ctypes.c_double, ctypes.c_double, _c_double_p, _c_double_p, _c_int_p, _c_double_p,
+                                        ctypes.c_int]),
     "calib_rectify_maps": (ctypes.c_int, [ctypes.c_int, _c_double_p, _c_double_p, _c_double_p, _c_double_p, ctypes.c_int,
                                           ctypes.c_int, _c_float_p, _c_float_p, ctypes.c_int]),
     "calib_rectify_points": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p,

@@ -5,6 +5,7 @@
 #include "undistort.hpp"
 #include "stereo.hpp"
 #include "stereo_joint.hpp"
+#include "rig.hpp"
 #include "rectify.hpp"
 #include "host_rows.hpp"
 #include "launch_plan.hpp"
@@ -876,7 +877,7 @@ bool shared_covariance(const double* red, int L, uint32_t fixed_mask, double sig
 // ============================================================================ C-ABI
 extern "C" {
 
-int calib_version(void) { return 460; }   // 4.6: calib_stereo_joint_normal_eq, calib_stereo_joint_step_delta, calib_refine_stereo_joint
+int calib_version(void) { return 470; }   // 4.7: calib_rig_normal_eq, calib_rig_step_delta, calib_refine_rig
 
 const char* calib_last_error(void) { return g_err.c_str(); }
 
@@ -2063,15 +2064,16 @@ int calib_remap(int dtype, const void* src, int src_h, int src_w, int channels, 
 
 }  // extern "C"
 
-// ---- stereo calibration: the host side of the LM loop both solvers share (stereo_loop.hpp), then the rig-only solver
-// ---- with both cameras known (stereo.hpp); the joint solver's own part follows the rectification section
+// ---- stereo calibration: the host side of the LM loop the solvers share (stereo_loop.hpp), then the rig-only solver
+// ---- with both cameras known (stereo.hpp); the joint solver's own part follows the rectification section, the
+// ---- multi-camera rig's (rig.hpp) the joint solver's
 namespace {
 
 struct StereoRun;
 
-// What differs between the two solvers on the host: the sizes of a problem's buffers and the launches of a round.
+// What differs between the solvers on the host: the sizes of a problem's buffers and the launches of a round.
 struct StereoSolver {
-    int S;                  // shared unknowns: the rig's 6, or LA + LB + 6
+    int S;                  // shared unknowns: the rig's 6, LA + LB + 6, or 6 (N - 1)
     int record;             // doubles per view record
     int ntot, nschur;       // entries per workgroup partial of the blocks / of the Schur kernel
     int views_a;            // views per workgroup of the blocks kernel (the Schur kernel: 16)
@@ -2115,31 +2117,33 @@ struct DoneWord {
     bool set() const { return *static_cast<volatile int*>(host) != 0; }
 };
 
-// Device side of one stereo call: the problem, the two (point, record, total) buffer sets the loop alternates between,
-// the state. Released with the scope of the entry point.
+// Device side of one stereo or rig call: the problem's cameras (two, or up to CALIB_RIG_MAX_CAMERAS), the two (point,
+// record, total) buffer sets the loop alternates between, the state. Released with the scope of the entry point.
 struct StereoRun {
     struct Cam {
         DevBuf<int64_t> offs;
         DevBuf<double2> uv;
-        DevBuf<double> xyz, shared;         // shared: the rig-only solver's known camera
+        DevBuf<double> xyz, shared;         // shared: a known camera (not the joint solver's)
         StereoCam view() const { return StereoCam{offs.p, uv.p, xyz.p}; }
     };
     StereoSolver sv{};
-    Cam a, b;
+    Cam cam[CALIB_RIG_MAX_CAMERAS];
     DevBuf<double> P[2], rec[2], partA[2], tot, partC, delta, trace;
     DevBuf<StereoState> st;
     DoneWord done;
     int64_t M = 0;
-    int nwgA = 0, nwgC = 0, model_a = 0, model_b = 0;
+    int nwgA = 0, nwgC = 0, ncam = 0, model[CALIB_RIG_MAX_CAMERAS] = {};
     StereoBufs bufs{};
 
     size_t params() const { return (size_t)sv.S + 6 * (size_t)M; }
     size_t trace_width() const { return (size_t)(CALIB_TRACE_HEADER + sv.S); }
 
-    static int upload_cam(Cam& c, int model, int64_t M, const int64_t* offs, const double* uv, const double* xyz,
-                          const double* shared) {
+    int upload_cam(int index, int model_id, int64_t M, const int64_t* offs, const double* uv, const double* xyz,
+                   const double* shared) {
+        Cam& c = cam[index];
+        model[index] = model_id;
         const int64_t n = offs[M];
-        const size_t L = 5 + (size_t)num_distortion(model);
+        const size_t L = 5 + (size_t)num_distortion(model_id);
         HIP_TRY(c.offs.alloc((size_t)M + 1));
         HIP_TRY(c.uv.alloc((size_t)std::max<int64_t>(n, 1)));
         HIP_TRY(c.xyz.alloc((size_t)std::max<int64_t>(n, 1) * 3));
@@ -2153,18 +2157,21 @@ struct StereoRun {
         return CALIB_OK;
     }
 
-    // the start point goes into buffer 0, which the bootstrap round evaluates as its candidate (cur = 1)
-    int begin(const StereoSolver& solver, bool joint, const calib_stereo_problem_t* p, const double* P0, uint64_t fixed_mask,
-              int max_iters, double lam, double lam_min, double lam_max, double err_min, bool want_trace, bool want_notify) {
+    // the two cameras of a stereo problem
+    int upload(bool joint, const calib_stereo_problem_t* p) {
+        ncam = 2;
+        const int rc = upload_cam(0, p->model_a, p->num_views, p->offs_a, p->uv_a, p->xyz_a, joint ? nullptr : p->shared_a);
+        return rc ? rc : upload_cam(1, p->model_b, p->num_views, p->offs_b, p->uv_b, p->xyz_b, joint ? nullptr : p->shared_b);
+    }
+
+    // After the cameras: the start point goes into buffer 0, which the bootstrap round evaluates as its candidate (cur = 1)
+    int begin(const StereoSolver& solver, int64_t num_views, const double* P0, uint64_t fixed_mask, int max_iters, double lam,
+              double lam_min, double lam_max, double err_min, bool want_trace, bool want_notify) {
         sv = solver;
-        M = p->num_views; model_a = p->model_a; model_b = p->model_b;
+        M = num_views;
         nwgA = (int)((M + sv.views_a - 1) / sv.views_a);
         nwgC = (int)((M + 15) / 16);
         const size_t K = params();
-        int rc = upload_cam(a, p->model_a, M, p->offs_a, p->uv_a, p->xyz_a, joint ? nullptr : p->shared_a);
-        if (rc) return rc;
-        rc = upload_cam(b, p->model_b, M, p->offs_b, p->uv_b, p->xyz_b, joint ? nullptr : p->shared_b);
-        if (rc) return rc;
         for (int s = 0; s < 2; ++s) {
             HIP_TRY(P[s].alloc(K));
             HIP_TRY(rec[s].alloc((size_t)M * sv.record));
@@ -2210,16 +2217,15 @@ int stereo_begin(StereoRun& run, bool joint, const calib_stereo_problem_t* p, co
     if (rc) return rc;
     rc = use_device(device_id);
     if (rc) return rc;
-    return run.begin(joint ? joint_solver(p->model_a, p->model_b) : rig_solver(), joint, p, P, fixed_mask, max_iters, lam,
+    rc = run.upload(joint, p);
+    if (rc) return rc;
+    return run.begin(joint ? joint_solver(p->model_a, p->model_b) : rig_solver(), p->num_views, P, fixed_mask, max_iters, lam,
                      lam_min, lam_max, err_min, want_trace, want_notify);
 }
 
 // the blocks at P on the host: every view's record and the totals
-int stereo_blocks(StereoRun& run, bool joint, const calib_stereo_problem_t* p, const double* P, int device_id,
-                  std::vector<double>& rec, std::vector<double>& tot) {
-    int rc = stereo_begin(run, joint, p, P, 0, 1, 0.0, 0.0, 0.0, 0.0, false, false, device_id);
-    if (rc) return rc;
-    rc = run.sv.evaluate(run);
+int run_blocks(StereoRun& run, std::vector<double>& rec, std::vector<double>& tot) {
+    int rc = run.sv.evaluate(run);
     if (rc) return rc;
     rec.resize((size_t)run.M * run.sv.record);
     tot.resize((size_t)run.sv.ntot);
@@ -2228,18 +2234,21 @@ int stereo_blocks(StereoRun& run, bool joint, const calib_stereo_problem_t* p, c
     return CALIB_OK;
 }
 
+int stereo_blocks(StereoRun& run, bool joint, const calib_stereo_problem_t* p, const double* P, int device_id,
+                  std::vector<double>& rec, std::vector<double>& tot) {
+    const int rc = stereo_begin(run, joint, p, P, 0, 1, 0.0, 0.0, 0.0, 0.0, false, false, device_id);
+    return rc ? rc : run_blocks(run, rec, tot);
+}
+
 // a 6 x 6 lower triangle stored row by row -> the full symmetric matrix
 void sym6(const double* t, double* o) {
     for (int r = 0; r < 6; ++r)
         for (int c = 0; c <= r; ++c) o[r * 6 + c] = o[c * 6 + r] = t[r * (r + 1) / 2 + c];
 }
 
-int stereo_step_delta(bool joint, const calib_stereo_problem_t* p, const double* P, uint64_t fixed_mask, double lambda,
-                      double* out_delta, int device_id) {
-    StereoRun run;
-    int rc = stereo_begin(run, joint, p, P, fixed_mask, 1, lambda, 0.0, 0.0, 0.0, false, false, device_id);
-    if (rc) return rc;
-    rc = run.sv.evaluate(run);
+// one step from a run begun with lambda
+int run_step_delta(StereoRun& run, double* out_delta) {
+    int rc = run.sv.evaluate(run);
     if (rc) return rc;
     rc = run.sv.step(run);
     if (rc) return rc;
@@ -2251,14 +2260,17 @@ int stereo_step_delta(bool joint, const calib_stereo_problem_t* p, const double*
     return CALIB_OK;
 }
 
-int stereo_refine(bool joint, const calib_stereo_problem_t* p, double* P_inout, uint64_t fixed_mask, int max_iters,
-                  double lam_init, double lam_min, double lam_max, double err_min, double* out_sse, double* out_sse_ab,
-                  int* out_iters, double* out_trace, int device_id) {
-    if (max_iters <= 0) return fail(CALIB_E_INVALID, "max_iters must be >= 1");
+int stereo_step_delta(bool joint, const calib_stereo_problem_t* p, const double* P, uint64_t fixed_mask, double lambda,
+                      double* out_delta, int device_id) {
     StereoRun run;
-    int rc = stereo_begin(run, joint, p, P_inout, fixed_mask, max_iters, lam_init, lam_min, lam_max, err_min,
-                          out_trace != nullptr, true, device_id);
-    if (rc) return rc;
+    const int rc = stereo_begin(run, joint, p, P, fixed_mask, 1, lambda, 0.0, 0.0, 0.0, false, false, device_id);
+    return rc ? rc : run_step_delta(run, out_delta);
+}
+
+// the loop of a run begun with its start point; out_sse_cam: the error per camera at the returned point
+int run_refine(StereoRun& run, double* P_inout, int max_iters, double* out_sse, double* out_sse_cam, int* out_iters,
+               double* out_trace) {
+    int rc;
     // round 0 evaluates the start point; round r >= 1 decides iteration r - 1. The host runs ahead of the device: the
     // done word in pinned memory stops the enqueueing (rounds already in the queue return at once); without such a word,
     // a synchronised look at the state every 8 rounds.
@@ -2282,21 +2294,32 @@ int stereo_refine(bool joint, const calib_stereo_problem_t* p, double* P_inout, 
     HIP_TRY(hipMemcpy(P_inout, run.P[s.cur].p, run.params() * 8, hipMemcpyDeviceToHost));
     if (out_sse) *out_sse = s.last_err;
     if (out_iters) *out_iters = s.iters;
-    if (out_sse_ab)     // the two errors end the totals
-        HIP_TRY(hipMemcpy(out_sse_ab, run.tot.p + (size_t)s.cur * run.sv.ntot + (run.sv.ntot - 2), 16, hipMemcpyDeviceToHost));
+    if (out_sse_cam)    // the cameras' errors end the totals
+        HIP_TRY(hipMemcpy(out_sse_cam, run.tot.p + (size_t)s.cur * run.sv.ntot + (run.sv.ntot - run.ncam), (size_t)run.ncam * 8,
+                          hipMemcpyDeviceToHost));
     if (out_trace && s.iters > 0)
         HIP_TRY(hipMemcpy(out_trace, run.trace.p, (size_t)s.iters * run.trace_width() * 8, hipMemcpyDeviceToHost));
     return CALIB_OK;
 }
 
+int stereo_refine(bool joint, const calib_stereo_problem_t* p, double* P_inout, uint64_t fixed_mask, int max_iters,
+                  double lam_init, double lam_min, double lam_max, double err_min, double* out_sse, double* out_sse_ab,
+                  int* out_iters, double* out_trace, int device_id) {
+    if (max_iters <= 0) return fail(CALIB_E_INVALID, "max_iters must be >= 1");
+    StereoRun run;
+    const int rc = stereo_begin(run, joint, p, P_inout, fixed_mask, max_iters, lam_init, lam_min, lam_max, err_min,
+                                out_trace != nullptr, true, device_id);
+    return rc ? rc : run_refine(run, P_inout, max_iters, out_sse, out_sse_ab, out_iters, out_trace);
+}
+
 int rig_evaluate(const StereoRun& r) {
-    const StereoCam ca = r.a.view(), cb = r.b.view();
+    const StereoCam ca = r.cam[0].view(), cb = r.cam[1].view();
     const StereoBufs bf = r.bufs;
     const unsigned grid = (unsigned)r.nwgA;
-    const int rc = dispatch_model(r.model_a, [&](auto fa) -> int {
-        return dispatch_model(r.model_b, [&](auto fb) -> int {
+    const int rc = dispatch_model(r.model[0], [&](auto fa) -> int {
+        return dispatch_model(r.model[1], [&](auto fb) -> int {
             hipLaunchKernelGGL((stereo_blocks_kernel<decltype(fa)::MODEL, decltype(fb)::MODEL>), dim3(grid), dim3(256),
-                               0, 0, ca, r.a.shared.p, cb, r.b.shared.p, bf);
+                               0, 0, ca, r.cam[0].shared.p, cb, r.cam[1].shared.p, bf);
             LAUNCHED(kNoHandle, "stereo_blocks_kernel");
             return CALIB_OK;
         });
@@ -2309,7 +2332,7 @@ int rig_evaluate(const StereoRun& r) {
 
 int rig_step(const StereoRun& r) {
     const StereoBufs bf = r.bufs;
-    hipLaunchKernelGGL(stereo_schur_kernel<16>, dim3((unsigned)r.nwgC), dim3(256), 0, 0, r.a.view(), r.b.view(), bf);
+    hipLaunchKernelGGL(stereo_schur_kernel<16>, dim3((unsigned)r.nwgC), dim3(256), 0, 0, r.cam[0].view(), r.cam[1].view(), bf);
     LAUNCHED(kNoHandle, "stereo_schur_kernel");
     hipLaunchKernelGGL(stereo_rig_kernel<kStSchur>, dim3(1), dim3(256), 0, 0, bf, r.nwgC);
     LAUNCHED(kNoHandle, "stereo_rig_kernel");
@@ -2523,11 +2546,11 @@ int dispatch_joint(int model_a, int model_b, F&& f) {
 }
 
 int joint_evaluate(const StereoRun& r) {
-    const StereoCam ca = r.a.view(), cb = r.b.view();
+    const StereoCam ca = r.cam[0].view(), cb = r.cam[1].view();
     const StereoBufs bf = r.bufs;
     const unsigned grid = (unsigned)r.nwgA;
     const int nwg = r.nwgA;
-    return dispatch_joint(r.model_a, r.model_b, [&](auto fa, auto fb) -> int {
+    return dispatch_joint(r.model[0], r.model[1], [&](auto fa, auto fb) -> int {
         constexpr int MA = decltype(fa)::MODEL, MB = decltype(fb)::MODEL;
         hipLaunchKernelGGL((stereo_joint_blocks_kernel<MA, MB>), dim3(grid), dim3(64 * kJWaves), 0, 0, ca, cb, bf);
         LAUNCHED(kNoHandle, "stereo_joint_blocks_kernel");
@@ -2539,11 +2562,11 @@ int joint_evaluate(const StereoRun& r) {
 }
 
 int joint_step(const StereoRun& r) {
-    const StereoCam ca = r.a.view(), cb = r.b.view();
+    const StereoCam ca = r.cam[0].view(), cb = r.cam[1].view();
     const StereoBufs bf = r.bufs;
     const int nwg = r.nwgC;
     const unsigned gridB = (unsigned)((r.M + 63) / 64);
-    return dispatch_joint(r.model_a, r.model_b, [&](auto fa, auto fb) -> int {
+    return dispatch_joint(r.model[0], r.model[1], [&](auto fa, auto fb) -> int {
         constexpr int LA = ModelTraits<decltype(fa)::MODEL>::L, LB = ModelTraits<decltype(fb)::MODEL>::L;
         using Y = JointLayout<LA, LB>;
         hipLaunchKernelGGL((stereo_joint_schur_kernel<LA, LB>), dim3((unsigned)nwg), dim3(256), 0, 0, ca, cb, bf);
@@ -2613,6 +2636,169 @@ int calib_refine_stereo_joint(const calib_stereo_problem_t* problem, double* Pj_
                               double* out_sse_ab, int* out_iters, double* out_trace, int device_id) {
     return stereo_refine(true, problem, Pj_inout, fixed_mask, max_iters, lam_init, lam_min, lam_max, err_min, out_sse,
                          out_sse_ab, out_iters, out_trace, device_id);
+}
+
+}  // extern "C"
+
+// ---- multi-camera rig calibration: N known cameras, one board (rig.hpp); the loop is the stereo section's ------------
+namespace {
+
+// the number of cameras of a rig call as a compile-time argument
+template <typename F>
+int dispatch_cameras(int n, F&& f) {
+    switch (n) {
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 5: return f(std::integral_constant<int, 5>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        case 7: return f(std::integral_constant<int, 7>{});
+        case 8: return f(std::integral_constant<int, 8>{});
+    }
+    return fail(CALIB_E_INVALID, "a rig has 2 to 8 cameras");
+}
+static_assert(CALIB_RIG_MAX_CAMERAS == kRigMaxCams, "the C ABI's camera count is the kernels'");
+
+int check_rig(const calib_rig_problem_t* p, const double* P) {
+    if (!p || !P || !p->cameras) return fail(CALIB_E_INVALID, "null argument");
+    if (p->num_cameras < 2 || p->num_cameras > CALIB_RIG_MAX_CAMERAS) return fail(CALIB_E_INVALID, "a rig has 2 to 8 cameras");
+    if (p->num_views < 1) return fail(CALIB_E_INVALID, "rig calibration needs at least one view");
+    for (int c = 0; c < p->num_cameras; ++c) {
+        const calib_rig_camera_t& cm = p->cameras[c];
+        if (!known_model(cm.model)) return fail(CALIB_E_INVALID, "unknown distortion model");
+        if (!cm.shared) return fail(CALIB_E_INVALID, "null argument");
+        const int rc = check_views(p->num_views, cm.offs, cm.uv, cm.xyz);
+        if (rc) return rc;
+    }
+    return CALIB_OK;
+}
+
+RigCams rig_cams(const StereoRun& r) {
+    RigCams rc{};
+    for (int c = 0; c < r.ncam; ++c) {
+        rc.cam[c] = r.cam[c].view();
+        rc.shared[c] = r.cam[c].shared.p;
+        rc.model[c] = r.model[c];
+    }
+    return rc;
+}
+
+int multi_evaluate(const StereoRun& r) {
+    const RigCams rc = rig_cams(r);
+    const StereoBufs bf = r.bufs;
+    const int nwg = r.nwgA;
+    return dispatch_cameras(r.ncam, [&](auto nc) -> int {
+        constexpr int NC = decltype(nc)::value;
+        hipLaunchKernelGGL(rig_blocks_kernel<NC>, dim3((unsigned)nwg), dim3(256), 0, 0, rc, bf);
+        LAUNCHED(kNoHandle, "rig_blocks_kernel");
+        hipLaunchKernelGGL(rig_decide_kernel<NC>, dim3(1), dim3(256), 0, 0, bf, nwg);
+        LAUNCHED(kNoHandle, "rig_decide_kernel");
+        return CALIB_OK;
+    });
+}
+
+int multi_step(const StereoRun& r) {
+    const RigCams rc = rig_cams(r);
+    const StereoBufs bf = r.bufs;
+    const int nwg = r.nwgC;
+    const unsigned gridB = (unsigned)((r.M + 63) / 64);
+    return dispatch_cameras(r.ncam, [&](auto nc) -> int {
+        constexpr int NC = decltype(nc)::value;
+        using Y = RigLayout<NC>;
+        hipLaunchKernelGGL(rig_schur_kernel<NC>, dim3((unsigned)nwg), dim3(256), 0, 0, rc, bf);
+        LAUNCHED(kNoHandle, "rig_schur_kernel");
+        hipLaunchKernelGGL(rig_solve_kernel<NC>, dim3(1), dim3(256), 0, 0, bf, nwg);
+        LAUNCHED(kNoHandle, "rig_solve_kernel");
+        hipLaunchKernelGGL((stereo_backsub_kernel<Y, Y::S>), dim3(gridB), dim3(64), 0, 0, bf);
+        LAUNCHED(kNoHandle, "rig_backsub_kernel");
+        return CALIB_OK;
+    });
+}
+
+int multi_singular() {
+    return fail(CALIB_E_SINGULAR, "rig normal equations singular: a view with fewer than three points over all cameras, or "
+                                  "a pivot of a view block or of the reduced system that is not positive (a camera other "
+                                  "than camera 0 that sees nothing)");
+}
+
+StereoSolver multi_solver(int num_cameras) {
+    StereoSolver sv{};
+    dispatch_cameras(num_cameras, [&](auto nc) -> int {
+        using Y = RigLayout<decltype(nc)::value>;
+        sv = StereoSolver{Y::S, Y::kStride, Y::kTot, Y::kSchur, 16, multi_evaluate, multi_step, multi_singular};
+        return CALIB_OK;
+    });
+    return sv;
+}
+
+// checks, device, the cameras and the run's buffers with P as the start point
+int multi_begin(StereoRun& run, const calib_rig_problem_t* p, const double* P, int max_iters, double lam, double lam_min,
+                double lam_max, double err_min, bool want_trace, bool want_notify, int device_id) {
+    int rc = check_rig(p, P);
+    if (rc) return rc;
+    rc = use_device(device_id);
+    if (rc) return rc;
+    run.ncam = p->num_cameras;
+    for (int c = 0; c < p->num_cameras; ++c) {
+        const calib_rig_camera_t& cm = p->cameras[c];
+        rc = run.upload_cam(c, cm.model, p->num_views, cm.offs, cm.uv, cm.xyz, cm.shared);
+        if (rc) return rc;
+    }
+    return run.begin(multi_solver(p->num_cameras), p->num_views, P, 0, max_iters, lam, lam_min, lam_max, err_min, want_trace,
+                     want_notify);
+}
+
+}  // namespace
+
+extern "C" {
+
+int calib_rig_normal_eq(const calib_rig_problem_t* problem, const double* Pr, double* out_B, double* out_E, double* out_V,
+                        double* out_g, double* out_sse_cam, int device_id) {
+    StereoRun run;
+    std::vector<double> rec, tot;
+    int rc = multi_begin(run, problem, Pr, 1, 0.0, 0.0, 0.0, 0.0, false, false, device_id);
+    if (rc) return rc;
+    rc = run_blocks(run, rec, tot);
+    if (rc) return rc;
+    const size_t M = (size_t)problem->num_views, S = (size_t)run.sv.S;
+    return dispatch_cameras(problem->num_cameras, [&](auto nc) -> int {
+        using Y = RigLayout<decltype(nc)::value>;
+        if (out_B)
+            for (int r = 0; r < Y::S; ++r)
+                for (int c = 0; c <= r; ++c) {
+                    const int slot = Y::slotB(r, c);
+                    out_B[r * S + c] = out_B[c * S + r] = slot >= 0 ? tot[(size_t)slot] : 0.0;
+                }
+        for (int c = 1; c < decltype(nc)::value; ++c) {
+            const double* g = tot.data() + Y::kCam * (c - 1) + 21;
+            if (out_g) std::copy(g, g + 6, out_g + 6 * (c - 1));
+        }
+        if (out_sse_cam) std::copy(tot.begin() + Y::kErr, tot.begin() + Y::kTot, out_sse_cam);
+        for (size_t v = 0; v < M; ++v) {
+            const double* r = rec.data() + v * Y::kStride;
+            if (out_V) sym6(r + Y::kV, out_V + v * 36);
+            if (out_E) std::copy(r + Y::kE, r + Y::kE + 6 * Y::S, out_E + v * 6 * S);
+            if (out_g) std::copy(r + Y::kGv, r + Y::kGv + 6, out_g + S + v * 6);
+        }
+        return CALIB_OK;
+    });
+}
+
+int calib_rig_step_delta(const calib_rig_problem_t* problem, const double* Pr, double lambda, double* out_delta,
+                         int device_id) {
+    StereoRun run;
+    const int rc = multi_begin(run, problem, Pr, 1, lambda, 0.0, 0.0, 0.0, false, false, device_id);
+    return rc ? rc : run_step_delta(run, out_delta);
+}
+
+int calib_refine_rig(const calib_rig_problem_t* problem, double* Pr_inout, int max_iters, double lam_init, double lam_min,
+                     double lam_max, double err_min, double* out_sse, double* out_sse_cam, int* out_iters, double* out_trace,
+                     int device_id) {
+    if (max_iters <= 0) return fail(CALIB_E_INVALID, "max_iters must be >= 1");
+    StereoRun run;
+    const int rc = multi_begin(run, problem, Pr_inout, max_iters, lam_init, lam_min, lam_max, err_min, out_trace != nullptr,
+                               true, device_id);
+    return rc ? rc : run_refine(run, Pr_inout, max_iters, out_sse, out_sse_cam, out_iters, out_trace);
 }
 
 }  // extern "C"

@@ -12,7 +12,7 @@
 
 namespace calib {
 
-constexpr int kJMaxS = 26;            // shared unknowns of the joint problem at most (two radtan cameras and the rig)
+constexpr int kJMaxS = 42;            // shared unknowns at most: the seven rigs of eight cameras (rig.hpp; the joint problem has 26)
 
 // one camera's correspondences (the rig-only solver's known cameras travel beside them: stereo_blocks_kernel)
 struct StereoCam {

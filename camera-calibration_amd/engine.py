@@ -887,6 +887,71 @@ def refineStereoJoint(cameraA, cameraB, Pj0, maxIters, fixedMask=0, lamInit=LAMB
     return sse.value, Pj, iters.value, trace[:iters.value], (float(ab[0]), float(ab[1]))
 
 
+# ---- multi-camera rig calibration with every camera known (calib_rig_*, csrc/rig.hpp) -------------------------------
+def _rigProblem(cameras, Pr):
+    """cameras: a sequence of 2 to 8 (modelId, shared (L,), viewOffsets (M+1,), sensorPoints (n,2), modelPoints (n,3)),
+    _stereoProblem's tuples -> (the C struct, the arrays it points into: keep them alive for the call, M, S,
+    Pr (S + 6 M,))"""
+    cameras = tuple(cameras)
+    N = len(cameras)
+    if not 2 <= N <= nat.RIG_MAX_CAMERAS:
+        raise ValueError(f"a rig has 2 to {nat.RIG_MAX_CAMERAS} cameras, got {N}")
+    arr = (nat.RigCamera * N)()
+    keep, M = [arr], None
+    for c, (modelId, shared, offs, s, m) in enumerate(cameras):
+        if modelId not in NUM_SHARED:
+            raise ValueError(f"camera {c}: unknown distortion model id {modelId!r}")
+        shared = np.ascontiguousarray(np.asarray(shared, dtype=np.float64).ravel())
+        if shared.shape[0] != NUM_SHARED[modelId]:
+            raise ValueError(f"camera {c}: expected {NUM_SHARED[modelId]} shared parameters, got {shared.shape[0]}")
+        offs, s, m = _packedViews(viewOffsets=offs, sensorPoints=s, modelPoints=m)
+        if M is not None and offs.shape[0] - 1 != M:
+            raise ValueError(f"cameras 0 and {c} have {M} and {offs.shape[0] - 1} views")
+        M = offs.shape[0] - 1
+        keep += [shared, offs, s, m]
+        arr[c] = nat.RigCamera(modelId, nat.i64ptr(offs), nat.dptr(s), nat.dptr(m), nat.dptr(shared))
+    S = 6 * (N - 1)
+    Pr = np.ascontiguousarray(np.asarray(Pr, dtype=np.float64).ravel())
+    if Pr.shape[0] != S + 6 * M:
+        raise ValueError(f"Expected shape ({S + 6 * M},) = ({N - 1} rigs, {M} poses), got {Pr.shape}")
+    return nat.RigProblem(N, M, arr), keep, M, S, Pr
+
+
+def rigNormalEquations(cameras, Pr, device=0):
+    """Block-arrow normal equations of the rig problem at Pr = (rig_1, .., rig_{N-1}, pose_0, ..) -> dict B (S,S), E (M,S,6)
+    [shared row, view column], V (M,6,6), g (S + 6 M,), sseCam (N,)."""
+    prob, keep, M, S, Pr = _rigProblem(cameras, Pr)
+    B, E, V, g = np.empty((S, S)), np.empty((M, S, 6)), np.empty((M, 6, 6)), np.empty(S + 6 * M)
+    cam = np.empty(prob.num_cameras)
+    nat.check(nat.loadLibrary().calib_rig_normal_eq(ctypes.byref(prob), nat.dptr(Pr), nat.dptr(B), nat.dptr(E), nat.dptr(V),
+                                                    nat.dptr(g), nat.dptr(cam), int(device)))
+    return {"B": B, "E": E, "V": V, "g": g, "sseCam": cam}
+
+
+def rigStepDelta(cameras, Pr, lam, device=0):
+    """delta (S + 6 M,) = (J^T J + lam diag J^T J)^-1 J^T r of the rig problem at Pr, solved on the device."""
+    prob, keep, M, S, Pr = _rigProblem(cameras, Pr)
+    delta = np.empty(S + 6 * M)
+    nat.check(nat.loadLibrary().calib_rig_step_delta(ctypes.byref(prob), nat.dptr(Pr), float(lam), nat.dptr(delta),
+                                                     int(device)))
+    return delta
+
+
+def refineRig(cameras, Pr0, maxIters, lamInit=LAMBDA_INITIAL, lamMin=LAMBDA_MIN, lamMax=LAMBDA_MAX, errMin=PT_ERROR_MIN,
+              device=0):
+    """The LM loop on Pr with every camera held fixed -> (sse [pre-update, as the reference returns], Pr, iters,
+    trace (iters, 5 + S), sseCam (N,) at the returned Pr)."""
+    prob, keep, M, S, Pr = _rigProblem(cameras, Pr0)
+    Pr = Pr.copy()
+    maxIters = int(maxIters)
+    sse, iters, cam = ctypes.c_double(0.0), ctypes.c_int(0), np.empty(prob.num_cameras)
+    trace = np.zeros((max(maxIters, 1), nat.TRACE_HEADER + S))
+    nat.check(nat.loadLibrary().calib_refine_rig(
+        ctypes.byref(prob), nat.dptr(Pr), maxIters, float(lamInit), float(lamMin), float(lamMax), float(errMin),
+        ctypes.byref(sse), nat.dptr(cam), ctypes.byref(iters), nat.dptr(trace), int(device)))
+    return sse.value, Pr, iters.value, trace[:iters.value], cam
+
+
 # ---- using a calibrated rig (calib_rectify_*, calib_triangulate, csrc/rectify.hpp): arguments are checked first --------
 def _rotation(R, name="R"):
     if R is None:

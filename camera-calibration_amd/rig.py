@@ -1,0 +1,151 @@
+"""Multi-camera rig calibration: where N known cameras sit relative to camera 0.
+
+stereo.py for N cameras, 2 <= N <= 8. The cameras see M views of one board; each camera's A and k stay as given. Unknowns
+are the N - 1 rigs (rig_c takes camera 0's frame into camera c's, Xc = R_c X0 + t_c) and the M board poses in camera 0's
+frame: ONE set of poses and one covariance tie the cameras together, which N - 1 stereoCalibrate calls pair by pair do
+not give. The start point is host arithmetic on per-view poses (estimatePoses per camera, on the device; a spanning tree
+over the camera pairs that share solved views), the refinement is the LM loop of the reference on the device
+(calib_refine_rig, csrc/rig.hpp), the covariance host arithmetic on the blocks of calib_rig_normal_eq.
+"""
+from collections import deque
+
+import numpy as np
+
+from . import engine
+from .main import calibrateCamera
+from .stereo import (RIG_NAMES, _camera, _solvedPoses, _views, averageTransform, invertPoses, jointCovarianceFromBlocks,
+                     parametersToPoses, posesToParameters)
+
+
+def rigStartPoints(W, ok):
+    """Start point of the rig refinement from per-camera, per-view board poses: W (N,M,4,4) board in camera c, ok (N,M)
+    which of them are solved. A breadth-first spanning tree from camera 0 over the camera pairs with at least one view
+    solved by both, neighbours tried in index order; an edge's transform is stereo.averageTransform over the views both
+    solved (rigStartPoint's average), composed along the tree. A view's start pose comes from the lowest-indexed camera
+    that solved it, carried into camera 0's frame. -> (T (N,4,4) camera 0's frame into camera c's, T[0] = I; W0 (M,4,4)).
+    ValueError naming the first view that no camera solved, or the first camera that no chain of shared views connects
+    to camera 0."""
+    W = np.asarray(W, dtype=np.float64)
+    ok = np.asarray(ok, dtype=bool)
+    if W.ndim != 4 or W.shape[2:] != (4, 4) or ok.shape != W.shape[:2]:
+        raise ValueError(f"expected W (N,M,4,4) and ok (N,M), got {W.shape} and {ok.shape}")
+    N, M = ok.shape
+    none = np.flatnonzero(~ok.any(axis=0))
+    if none.size:
+        raise ValueError(f"view {int(none[0])}: no camera has a solved board pose")
+    T = np.tile(np.eye(4), (N, 1, 1))
+    reached = np.zeros(N, dtype=bool)
+    reached[0] = True
+    queue = deque([0])
+    while queue:
+        a = queue.popleft()
+        for b in range(N):
+            both = ok[a] & ok[b]
+            if reached[b] or not both.any():
+                continue
+            T[b] = averageTransform(W[a][both], W[b][both]) @ T[a]
+            reached[b] = True
+            queue.append(b)
+    if not reached.all():
+        raise ValueError(f"camera {int(np.flatnonzero(~reached)[0])}: no chain of views that two cameras both solved "
+                         "connects it to camera 0: its rig has no start point")
+    first = np.argmax(ok, axis=0)                                  # the lowest-indexed camera that solved the view
+    W0 = invertPoses(T)[first] @ W[first, np.arange(M)]
+    return T, W0
+
+
+class RigCalibration:
+    """Result of rigCalibrate: T (N,4,4) camera 0's frame into camera c's (T[0] = I), W list of (4,4) board in camera 0,
+    Pr the parameter vector (rig_1, .., rig_{N-1}, pose_0, ..), sse the error AT the result (= sseCam.sum()), sseCam /
+    numPoints / rms (N,) per camera (rms NaN for a camera without points), iters, trace (iters, 5 + S).
+    sseBeforeLastUpdate is what the refinement itself returns, the reference's convention (src/calibrate.py:171)."""
+
+    def __init__(self, sseBeforeLastUpdate, Pr, iters, trace, sseCam, problem, device):
+        N = len(problem)
+        S = 6 * (N - 1)
+        self.Pr, self.iters, self.trace, self.sseBeforeLastUpdate = Pr, iters, trace, sseBeforeLastUpdate
+        self.sseCam = np.asarray(sseCam, dtype=np.float64)
+        self.sse = float(self.sseCam.sum())
+        self.T = np.concatenate((np.eye(4)[None], parametersToPoses(Pr[:S])))
+        self.W = list(parametersToPoses(Pr[S:]))
+        self.numPoints = np.array([int(cam[2][-1]) for cam in problem], dtype=np.int64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            self.rms = np.where(self.numPoints > 0, np.sqrt(self.sseCam / self.numPoints), np.nan)
+        self._problem, self._device = problem, device
+
+    @property
+    def numCameras(self):
+        return len(self._problem)
+
+    def transform(self, a, b):
+        """(4,4) camera a's frame into camera b's: Xb = R Xa + t"""
+        return self.T[b] @ invertPoses(self.T[a][None])[0]
+
+    def covariance(self):
+        """Covariance (S,S) of the rig parameters (parameterNames) at the result: sigma^2 S_undamped^-1 with
+        sigma^2 = sse / (2 n - S - 6 M), the units of CalibrationUncertainty."""
+        ne = engine.rigNormalEquations(self._problem, self.Pr, self._device)
+        return jointCovarianceFromBlocks(ne["B"], ne["E"], ne["V"], float(ne["sseCam"].sum()), int(self.numPoints.sum()))
+
+    def rigCovariance(self, c):
+        """the 6 x 6 block of covariance() of camera c >= 1 (rho_x, rho_y, rho_z in DEGREES, then t)"""
+        if not 1 <= c < self.numCameras:
+            raise ValueError(f"camera {c!r} has no rig: expected 1 <= c < {self.numCameras}")
+        return self.covariance()[6 * (c - 1):6 * c, 6 * (c - 1):6 * c].copy()
+
+    def parameterNames(self):
+        """names of the S rig unknowns: rig1.rx .. rig{N-1}.tz"""
+        return tuple(f"rig{c}.{n}" for c in range(1, self.numCameras) for n in RIG_NAMES)
+
+    def cameras(self):
+        """the cameras, each (distortionType, A, k) as rigCalibrate took it"""
+        names = {v: n for n, v in engine.MODEL_IDS.items()}
+        return tuple((names[modelId], np.array([[s[0], s[2], s[3]], [0.0, s[1], s[4]], [0.0, 0.0, 1.0]]), s[5:].copy())
+                     for modelId, s in ((c[0], np.asarray(c[1], dtype=np.float64)) for c in self._problem))
+
+    def rectify(self, a, b, size, **kw):
+        """rectify.stereoRectify for the pair (a, b): size = (width, height) of the images -> StereoRectification"""
+        from . import rectify
+        kw.setdefault("device", self._device)
+        cams, T = self.cameras(), self.transform(a, b)
+        return rectify.stereoRectify(cams[a], cams[b], T[:3, :3].copy(), T[:3, 3].copy(), size, **kw)
+
+    def triangulate(self, a, b, uvA, uvB, returnStatus=False, returnError=False):
+        """rectify.triangulate for the pair (a, b): matched pixels (n,2) of the two cameras -> X (n,3) in camera a's frame"""
+        from . import rectify
+        cams, T = self.cameras(), self.transform(a, b)
+        return rectify.triangulate(cams[a], cams[b], T[:3, :3].copy(), T[:3, 3].copy(), uvA, uvB, returnStatus, returnError,
+                                   self._device)
+
+
+def rigCalibrate(detections, cameras, maxIters=50, device=0):
+    """The rigs between N KNOWN cameras, 2 <= N <= 8. cameras[c] = (distortionType, A (3,3), k); detections[c]: a list of
+    length M, entry i a (sensor (n,2), model (n,3)) pair of view i in camera c, or None / empty where the camera did not
+    see the board (the cameras may see different corners). -> RigCalibration."""
+    if len(detections) != len(cameras) or not 2 <= len(cameras) <= 8:
+        raise ValueError(f"expected 2 to 8 cameras and a detection list for each, got {len(cameras)} and {len(detections)}")
+    cams = [_camera(cam, c) for c, cam in enumerate(cameras)]
+    views = [_views(dets, c) for c, dets in enumerate(detections)]
+    M = len(views[0])
+    if M < 1 or any(len(v) != M for v in views):
+        raise ValueError(f"expected detection lists of one length >= 1, got {[len(v) for v in views]}")
+    solved = [_solvedPoses(cam, v, 20, device) for cam, v in zip(cams, views)]
+    T0, W0 = rigStartPoints(np.stack([W for W, _ in solved]), np.stack([ok for _, ok in solved]))
+    Pr0 = np.concatenate((posesToParameters(T0[1:]).ravel(), posesToParameters(W0).ravel()))
+    problem = tuple((cam[1], cam[4]) + engine.packDetections(v) for cam, v in zip(cams, views))
+    sse, Pr, iters, trace, sseCam = engine.refineRig(problem, Pr0, maxIters, device=device)
+    return RigCalibration(sse, Pr, iters, trace, sseCam, problem, device)
+
+
+def calibrateRig(detections, types, maxIters, device=0):
+    """Every camera from scratch, then the rigs: calibrateCamera on each camera's own non-empty views, then rigCalibrate
+    with the results held fixed. -> (results, rig), results[c] = (sse, A, W, k) as calibrateCamera returns it (W over that
+    camera's non-empty views, in order)."""
+    if len(detections) != len(types):
+        raise ValueError(f"expected a distortion type per camera, got {len(types)} for {len(detections)} cameras")
+    results = []
+    for c, (dets, distortionType) in enumerate(zip(detections, types)):
+        own = [v for v in _views(dets, c) if v[0].shape[0] > 0]
+        results.append(calibrateCamera(own, distortionType, maxIters, device=device))
+    rig = rigCalibrate(detections, [(t, A, k) for t, (_, A, _, k) in zip(types, results)], maxIters, device)
+    return results, rig

@@ -52,6 +52,15 @@ def invertPoses(W):
     return mu.posesFromRT(Rt, -np.einsum("nij,nj->ni", Rt, W[:, :3, 3]))
 
 
+def averageTransform(Wa, Wb):
+    """Wa, Wb (n,4,4) board in camera a / b, n >= 1 -> (4,4) camera a's frame into camera b's: T_i = Wb_i Wa_i^-1, the
+    rotation nearest sum R_i (SVD, determinant fixed) and the mean t_i"""
+    T = Wb @ invertPoses(Wa)
+    U, _, Vt = np.linalg.svd(T[:, :3, :3].sum(axis=0))
+    R0 = U @ np.diag([1.0, 1.0, np.linalg.det(U @ Vt)]) @ Vt
+    return mu.poseFromRT(R0, T[:, :3, 3].mean(axis=0))
+
+
 def rigStartPoint(Wa, Wb, okA, okB):
     """Start point of the stereo refinement from per-view board poses: Wa, Wb (M,4,4) board in camera a / b, okA, okB
     (M,) which of them are solved. T_i = Wb_i Wa_i^-1 over the views both cameras solved; R0 = the rotation nearest
@@ -66,10 +75,7 @@ def rigStartPoint(Wa, Wb, okA, okB):
     both = okA & okB
     if not both.any():
         raise ValueError("no view has a solved board pose in both cameras: the rig has no start point")
-    T = Wb[both] @ invertPoses(Wa[both])
-    U, _, Vt = np.linalg.svd(T[:, :3, :3].sum(axis=0))
-    R0 = U @ np.diag([1.0, 1.0, np.linalg.det(U @ Vt)]) @ Vt
-    T0 = mu.poseFromRT(R0, T[:, :3, 3].mean(axis=0))
+    T0 = averageTransform(Wa[both], Wb[both])
     W0 = Wa.copy()
     onlyB = ~okA
     if onlyB.any():

@@ -434,6 +434,45 @@ int calib_refine_stereo_joint(const calib_stereo_problem_t* problem, double* Pj_
                               double lam_init, double lam_min, double lam_max, double err_min, double* out_sse,
                               double* out_sse_ab, int* out_iters, double* out_trace, int device_id);
 
+/* ---- multi-camera rig calibration: N KNOWN cameras, one board -----------------------------------------------------
+ * N cameras, 2 <= N <= CALIB_RIG_MAX_CAMERAS, each radtan or fisheye with its shared vector held fixed, see M views of
+ * one board; each camera's correspondences are a CSR of its own (the cameras may see different corners, any camera's
+ * side of a view may be empty). Camera 0 is the reference frame. Unknowns Pr (S + 6 M) = (rig_1, .., rig_{N-1}, pose_0,
+ * .., pose_{M-1}), S = 6 (N - 1) <= 42, the 6-tuples as in Ps: pose_i takes board points into camera 0's frame, rig_c takes
+ * camera 0's frame into camera c's, Xc = R_c X0 + t_c. Residuals uv_c - project_c(Xc); the error is the sum of their
+ * squared norms over all cameras. With N = 2 the problem is calib_refine_stereo's. Stateless, host pointers, any output
+ * may be NULL, fixed-order sums (a call is bitwise reproducible). N outside [2, 8], a bad model id, num_views < 1,
+ * max_iters <= 0, a NULL input or an offset array that does not start at 0 or decreases is CALIB_E_INVALID before any
+ * device call.
+ *
+ * calib_rig_normal_eq: out_B (S,S) block diagonal, one 6 x 6 block per camera c >= 1; out_E (M,S,6) shared row x view
+ *   column, the 6 x 6 block of a camera that did not see the view exactly zero; out_V (M,6,6); out_g (S + 6 M) = J^T r in
+ *   the order of Pr; out_sse_cam (N) the error per camera.
+ * calib_rig_step_delta: delta (S + 6 M) = the LM step at Pr through the Schur complement of the view blocks.
+ * calib_refine_rig: the loop of calib_refine_stereo on Pr; out_sse = err(Pr) before the last update, out_sse_cam (N) the
+ *   error per camera AT the returned Pr, out_trace rows are CALIB_TRACE_HEADER + S doubles, the rigs before the update.
+ * CALIB_E_SINGULAR (Pr_inout left as it was): a view with fewer than three points over all cameras, an empty view, a
+ *   pivot of a view block or of the reduced system that is not positive -- a camera c >= 1 that sees nothing. Camera 0
+ *   seeing nothing is a solvable problem. */
+#define CALIB_RIG_MAX_CAMERAS 8
+typedef struct {
+    int model;
+    const int64_t* offs; const double *uv, *xyz, *shared;
+} calib_rig_camera_t;
+typedef struct {
+    int num_cameras;
+    int64_t num_views;
+    const calib_rig_camera_t* cameras;
+} calib_rig_problem_t;
+
+int calib_rig_normal_eq(const calib_rig_problem_t* problem, const double* Pr, double* out_B, double* out_E, double* out_V,
+                        double* out_g, double* out_sse_cam, int device_id);
+int calib_rig_step_delta(const calib_rig_problem_t* problem, const double* Pr, double lambda, double* out_delta,
+                         int device_id);
+int calib_refine_rig(const calib_rig_problem_t* problem, double* Pr_inout, int max_iters, double lam_init, double lam_min,
+                     double lam_max, double err_min, double* out_sse, double* out_sse_cam, int* out_iters, double* out_trace,
+                     int device_id);
+
 /* ---- using a calibrated rig: rectify maps, rectified points, triangulation ---------------------------------------
  * Stateless, host pointers, the work runs on device_id; cameras as in the undistortion entries (A (3,3) row-major, k the
  * model's coefficients). R is a (3,3) row-major rotation; |det R - 1| > 1e-6 is CALIB_E_INVALID, as are a bad model id, a
