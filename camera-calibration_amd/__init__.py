@@ -12,7 +12,7 @@ from .engine import RefineEngine  # noqa: F401
 from .jacobian import HomographyJacobian, ProjectionJacobian, createJacRadTan  # noqa: F401
 from .main import calibrateCamera, calibrateCameraExtended, estimatePoses  # noqa: F401
 from .rectify import (StereoRectification, optimalNewCameraMatrix, rectifyRotations, stereoRectify,  # noqa: F401
-                      triangulate)
+                      triangulate, triangulateMulti)
 from .rig import RigCalibration, calibrateRig, rigCalibrate, rigStartPoints  # noqa: F401
 from .stereo import StereoCalibration, calibrateStereo, stereoCalibrate  # noqa: F401
 from .uncertainty import CalibrationUncertainty  # noqa: F401

@@ -52,6 +52,14 @@ class RigProblem(ctypes.Structure):
 
 _rig_p = ctypes.POINTER(RigProblem)
 
+
+class ViewCamera(ctypes.Structure):
+    """calib_view_camera_t"""
+    _fields_ = [("model", ctypes.c_int), ("A", _c_double_p), ("k", _c_double_p), ("R", _c_double_p), ("t", _c_double_p)]
+
+
+_c_uint32_p = ctypes.POINTER(ctypes.c_uint32)
+
 # name -> (restype, argtypes); must list every symbol include/calib_lm.h declares
 SIGNATURES = {
     "calib_version": (ctypes.c_int, []),
@@ -159,6 +167,9 @@ SIGNATURES = {
     "calib_triangulate": (ctypes.c_int, [ctypes.c_int, _c_double_p, _c_double_p, ctypes.c_int, _c_double_p, _c_double_p,
                                          _c_double_p, _c_double_p, ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p,
                                          _c_double_p, _c_int32_p, ctypes.c_int]),
+    "calib_triangulate_multi": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ViewCamera), ctypes.c_int64, _c_double_p,
+                                               _c_uint32_p, _c_double_p, _c_double_p, _c_int32_p, _c_double_p, _c_double_p,
+                                               ctypes.c_int]),
 }
 
 _lib = None

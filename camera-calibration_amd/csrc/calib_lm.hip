@@ -7,6 +7,7 @@
 #include "stereo_joint.hpp"
 #include "rig.hpp"
 #include "rectify.hpp"
+#include "triangulate_multi.hpp"
 #include "host_rows.hpp"
 #include "launch_plan.hpp"
 #include "shard_layout.hpp"
@@ -877,7 +878,7 @@ bool shared_covariance(const double* red, int L, uint32_t fixed_mask, double sig
 // ============================================================================ C-ABI
 extern "C" {
 
-int calib_version(void) { return 470; }   // 4.7: calib_rig_normal_eq, calib_rig_step_delta, calib_refine_rig
+int calib_version(void) { return 480; }   // 4.8: calib_triangulate_multi
 
 const char* calib_last_error(void) { return g_err.c_str(); }
 
@@ -2799,6 +2800,92 @@ int calib_refine_rig(const calib_rig_problem_t* problem, double* Pr_inout, int m
     const int rc = multi_begin(run, problem, Pr_inout, max_iters, lam_init, lam_min, lam_max, err_min, out_trace != nullptr,
                                true, device_id);
     return rc ? rc : run_refine(run, Pr_inout, max_iters, out_sse, out_sse_cam, out_iters, out_trace);
+}
+
+}  // extern "C"
+
+// ---- N-view triangulation: one point from every camera of a rig that saw it (triangulate_multi.hpp) ----------------
+extern "C" {
+
+int calib_triangulate_multi(int num_cameras, const calib_view_camera_t* cameras, int64_t n, const double* uv,
+                            const uint32_t* seen, double* out_X, double* out_sse, int32_t* out_status, double* out_cov,
+                            double* out_res, int device_id) {
+    if (num_cameras < 2 || num_cameras > CALIB_RIG_MAX_CAMERAS) return fail(CALIB_E_INVALID, "a rig has 2 to 8 cameras");
+    if (!cameras || n < 0 || (n > 0 && (!uv || !out_X))) return fail(CALIB_E_INVALID, "null argument");
+    const size_t N = (size_t)num_cameras;
+    TriCameras cs{};
+    cs.n = num_cameras;
+    for (size_t c = 0; c < N; ++c) {
+        const calib_view_camera_t& in = cameras[c];
+        TriCamera& cm = cs.c[c];
+        if (!in.A || !in.k) return fail(CALIB_E_INVALID, "null argument");
+        if (!known_model(in.model)) return fail(CALIB_E_INVALID, "unknown distortion model");
+        if (!pinhole_of(in.A, cm.cam)) return fail(CALIB_E_INVALID, "alpha and beta of a camera matrix must not be 0");
+        if (!rotation_of(in.R, cm.T.R)) return fail(CALIB_E_INVALID, "R is not a rotation (|det R - 1| > 1e-6)");
+        for (int j = 0; j < 3; ++j) cm.T.t[j] = in.t ? in.t[j] : 0.0;
+        for (int j = 0; j < num_distortion(in.model); ++j) cm.k[j] = in.k[j];
+        cm.model = in.model;
+    }
+    const uint32_t all = (1u << num_cameras) - 1u;
+    if (seen)
+        for (int64_t i = 0; i < n; ++i)
+            if (seen[i] & ~all) return fail(CALIB_E_INVALID, "seen: a bit at or above the number of cameras is set");
+    if (n == 0) return CALIB_OK;
+    int rc = use_device(device_id);
+    if (rc) return rc;
+
+    // pixels -> distorted normalised points, camera-major like uv; an unseen pixel is not read: its slot holds 0
+    const size_t cnt = (size_t)n;
+    std::vector<double> norm(N * cnt * 2, 0.0);
+    std::vector<uint32_t> mask(cnt, all);
+    if (seen) std::copy(seen, seen + cnt, mask.begin());
+    for (size_t c = 0; c < N; ++c) {
+        const Pinhole& cam = cs.c[c].cam;
+        const double* src = uv + c * cnt * 2;
+        double* dst = norm.data() + c * cnt * 2;
+        for (size_t i = 0; i < cnt; ++i) {
+            if (!((mask[i] >> c) & 1u)) continue;
+            const double yd = (src[2 * i + 1] - cam.vc) / cam.be;
+            dst[2 * i] = (src[2 * i] - cam.uc - cam.ga * yd) / cam.al;
+            dst[2 * i + 1] = yd;
+        }
+    }
+    DevBuf<double2> duv, dxd, dxy, dres;
+    DevBuf<double> dk, dX, dsse, dcov;
+    DevBuf<int32_t> dinv, dstatus;
+    DevBuf<uint32_t> dseen;
+    HIP_TRY(duv.alloc(N * cnt)); HIP_TRY(dxd.alloc(N * cnt)); HIP_TRY(dxy.alloc(N * cnt)); HIP_TRY(dinv.alloc(N * cnt));
+    HIP_TRY(dk.alloc(N * 5)); HIP_TRY(dseen.alloc(cnt));
+    HIP_TRY(dX.alloc(cnt * 3)); HIP_TRY(dsse.alloc(cnt)); HIP_TRY(dstatus.alloc(cnt));
+    if (out_cov) HIP_TRY(dcov.alloc(cnt * 6));
+    if (out_res) HIP_TRY(dres.alloc(N * cnt));
+    std::vector<double> kAll(N * 5, 0.0);
+    for (size_t c = 0; c < N; ++c) std::copy(cs.c[c].k, cs.c[c].k + 5, kAll.begin() + 5 * c);
+    HIP_TRY(hipMemcpy(duv.p, uv, N * cnt * 16, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dxd.p, norm.data(), N * cnt * 16, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dk.p, kAll.data(), N * 5 * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dseen.p, mask.data(), cnt * 4, hipMemcpyHostToDevice));
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    for (size_t c = 0; c < N; ++c) {            // the ideal normalised points, as calib_undistort_points finds them
+        rc = dispatch_model(cs.c[c].model, [&](auto form) -> int {
+            hipLaunchKernelGGL((undistort_points_kernel<decltype(form)::MODEL>), dim3(blocks), dim3(256), 0, 0,
+                               (const double2*)(dxd.p + c * cnt), (const double*)(dk.p + 5 * c), n, dxy.p + c * cnt,
+                               dinv.p + c * cnt);
+            LAUNCHED(kNoHandle, "undistort_points_kernel");
+            return CALIB_OK;
+        });
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(triangulate_multi_kernel<256>, dim3(blocks), dim3(256), 0, 0, cs, n, (const double2*)duv.p,
+                       (const double2*)dxy.p, (const int32_t*)dinv.p, (const uint32_t*)dseen.p, dX.p, dsse.p, dstatus.p,
+                       dcov.p, dres.p);
+    LAUNCHED(kNoHandle, "triangulate_multi_kernel");
+    HIP_TRY(hipMemcpy(out_X, dX.p, cnt * 24, hipMemcpyDeviceToHost));
+    if (out_sse) HIP_TRY(hipMemcpy(out_sse, dsse.p, cnt * 8, hipMemcpyDeviceToHost));
+    if (out_status) HIP_TRY(hipMemcpy(out_status, dstatus.p, cnt * 4, hipMemcpyDeviceToHost));
+    if (out_cov) HIP_TRY(hipMemcpy(out_cov, dcov.p, cnt * 48, hipMemcpyDeviceToHost));
+    if (out_res) HIP_TRY(hipMemcpy(out_res, dres.p, N * cnt * 16, hipMemcpyDeviceToHost));
+    return CALIB_OK;
 }
 
 }  // extern "C"

@@ -1029,3 +1029,47 @@ def triangulate(modelIdA, Aa, ka, modelIdB, Ab, kb, R, t, uvA, uvB, device=0):
         nat.dptr(uvA), nat.dptr(uvB), nat.dptr(X), nat.dptr(sse),
         status.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(device)))
     return X, sse, status
+
+
+def triangulateMulti(cameras, T, uv, seen=None, wantCov=False, wantRes=False, device=0):
+    """One point from every camera that saw it (calib_triangulate_multi, csrc/triangulate_multi.hpp). cameras: 2 to 8
+    (modelId, A, k); T (N,4,4): X_c = T[c] X; uv (N,n,2) camera-major pixels; seen (n,) uint32 with bit c set where
+    camera c saw the point, or None = all -> (X (n,3) in the frame the T map from, sse (n,), status (n,) int32: 0 ok,
+    1 no inverse, 2 degenerate geometry, 3 not converged, 4 fewer than two cameras; cov (n,6) the lower triangle of
+    (J^T J)^-1 at X or None; res (N,n,2) the residuals at X, NaN for an unseen camera, or None). NaN where status != 0."""
+    cameras = tuple(cameras)
+    N = len(cameras)
+    if not 2 <= N <= nat.RIG_MAX_CAMERAS:
+        raise ValueError(f"cameras: expected 2 to {nat.RIG_MAX_CAMERAS} cameras, got {N}")
+    T = np.asarray(T, dtype=np.float64)
+    if T.shape != (N, 4, 4):
+        raise ValueError(f"T: expected shape ({N}, 4, 4), got {T.shape}")
+    uv = np.asarray(uv, dtype=np.float64)
+    if uv.ndim != 3 or uv.shape[0] != N or uv.shape[2] != 2:
+        raise ValueError(f"uv: expected shape ({N}, None, 2), got {uv.shape}")
+    uv = np.ascontiguousarray(uv)
+    n = uv.shape[1]
+    if seen is not None:
+        seen = np.asarray(seen)
+        if seen.shape != (n,) or seen.dtype.kind not in "ui":
+            raise ValueError(f"seen: expected {n} unsigned integers, got shape {seen.shape} of {seen.dtype}")
+        if n and (int(seen.min()) < 0 or int(seen.max()) >> N):
+            raise ValueError(f"seen: a mask has bits outside the {N} cameras")
+        seen = np.ascontiguousarray(seen, dtype=np.uint32)
+    arr = (nat.ViewCamera * N)()
+    keep = []
+    for c, (modelId, A, k) in enumerate(cameras):
+        A, k = _cameraMatrix(A, f"A of camera {c}"), _coefficients(modelId, k)
+        R = _rotation(np.ascontiguousarray(T[c, :3, :3]), f"T[{c}]")
+        t = np.ascontiguousarray(T[c, :3, 3])
+        keep += [A, k, R, t]
+        arr[c] = nat.ViewCamera(modelId, nat.dptr(A), nat.dptr(k), nat.dptr(R), nat.dptr(t))
+    X, sse, status = np.empty((n, 3)), np.empty(n), np.empty(n, dtype=np.int32)
+    cov = np.empty((n, 6)) if wantCov else None
+    res = np.empty((N, n, 2)) if wantRes else None
+    nat.requireDevice()
+    nat.check(nat.loadLibrary().calib_triangulate_multi(
+        N, arr, n, nat.dptr(uv), None if seen is None else seen.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+        nat.dptr(X), nat.dptr(sse), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), nat.dptr(cov), nat.dptr(res),
+        int(device)))
+    return X, sse, status, cov, res

@@ -4,7 +4,8 @@ The reference stops at one camera; this is surface beside it, like undistort.py 
 the rig (Xb = R Xa + t); here that rig is used. The rectifying rotations, the projection matrices and the choice of the
 focal length are host arithmetic (numpy); what runs per pixel or per point runs on the device: the maps
 (calib_rectify_maps), the inverse model under rectifyPoints and under the focal length's sample grid
-(calib_undistort_points), the resampling (calib_remap) and the triangulation (calib_triangulate, csrc/rectify.hpp).
+(calib_undistort_points), the resampling (calib_remap) and the triangulation (calib_triangulate, csrc/rectify.hpp; from
+every camera of a rig at once: calib_triangulate_multi, csrc/triangulate_multi.hpp).
 """
 import numpy as np
 
@@ -270,4 +271,46 @@ def triangulate(cameraA, cameraB, R, t, uvA, uvB, returnStatus=False, returnErro
     camA, camB = _camera(cameraA, "a"), _camera(cameraB, "b")
     X, sse, status = engine.triangulate(camA[1], camA[2], camA[3], camB[1], camB[2], camB[3], R, t, uvA, uvB, device)
     out = (X,) + ((status,) if returnStatus else ()) + ((sse,) if returnError else ())
+    return out[0] if len(out) == 1 else out
+
+
+def seenMasks(uv):
+    """(N,n,2) pixels -> (n,) uint32: bit c set where both coordinates of camera c's pixel are finite"""
+    ok = np.isfinite(uv).all(axis=2)
+    return (ok.astype(np.uint32) << np.arange(uv.shape[0], dtype=np.uint32)[:, None]).sum(axis=0, dtype=np.uint32)
+
+
+def triangulateMulti(cameras, T, uv, seen=None, returnStatus=False, returnError=False, returnCovariance=False,
+                     returnResiduals=False, sigma=1.0, device=0):
+    """One 3-D point from every camera that saw it: cameras[c] = (distortionType, A (3,3), k), 2 to 8 of them; T (N,4,4)
+    with X_c = T[c] X (RigCalibration.T: X in camera 0's frame); uv (N,n,2), or a list of N (n,2) arrays, the pixels of
+    the n points in each camera; seen (n,) unsigned integers, bit c set where camera c saw the point -- None: a camera
+    saw a point where both coordinates of its pixel are finite. A camera that did not see a point adds nothing to it.
+    -> X (n,3), the minimiser of the pixel residuals of the cameras that saw the point under each camera's full model
+    (start: the point closest to the rays; then damped Gauss-Newton on the device). returnStatus adds the (n,) int32
+    status -- 0 ok, 1 a seen pixel without an inverse, 2 degenerate geometry, 3 not converged, 4 fewer than two cameras
+    saw the point; every output is NaN where it is not 0 --, returnError the (n,) squared pixel error at X,
+    returnCovariance the (n,3,3) covariance sigma^2 (J^T J)^-1 of X for pixel noise of standard deviation sigma, and
+    returnResiduals the (N,n,2) residuals at X, NaN for a camera that did not see the point."""
+    cams = [_camera(cam, c) for c, cam in enumerate(cameras)]
+    if isinstance(uv, (list, tuple)):
+        if len(uv) != len(cams):
+            raise ValueError(f"uv: expected a pixel array per camera ({len(cams)}), got {len(uv)}")
+        parts = [np.asarray(p, dtype=np.float64) for p in uv]
+        if any(p.ndim != 2 or p.shape != parts[0].shape or p.shape[1] != 2 for p in parts):
+            raise ValueError(f"uv: expected arrays of one shape (None, 2), got {[p.shape for p in parts]}")
+        uv = np.stack(parts)
+    uv = np.asarray(uv, dtype=np.float64)
+    if uv.ndim != 3 or uv.shape[0] != len(cams) or uv.shape[2] != 2:
+        raise ValueError(f"uv: expected shape ({len(cams)}, None, 2), got {uv.shape}")
+    if seen is None:
+        seen = seenMasks(uv)
+    X, sse, status, cov, res = engine.triangulateMulti([(cam[1], cam[2], cam[3]) for cam in cams], T, uv, seen,
+                                                       returnCovariance, returnResiduals, device)
+    out = (X,) + ((status,) if returnStatus else ()) + ((sse,) if returnError else ())
+    if returnCovariance:
+        full = cov[:, [0, 1, 3, 1, 2, 4, 3, 4, 5]].reshape(-1, 3, 3)
+        out += (float(sigma) ** 2 * full,)
+    if returnResiduals:
+        out += (res,)
     return out[0] if len(out) == 1 else out

@@ -117,6 +117,14 @@ class RigCalibration:
         return rectify.triangulate(cams[a], cams[b], T[:3, :3].copy(), T[:3, 3].copy(), uvA, uvB, returnStatus, returnError,
                                    self._device)
 
+    def triangulateAll(self, uv, seen=None, **kw):
+        """rectify.triangulateMulti with the rig's own cameras and T: uv (N,n,2), or a list of N (n,2) arrays, the pixels
+        of n points in every camera (not finite, or masked out by seen, where a camera did not see the point) -> X (n,3)
+        in camera 0's frame, from all the cameras that saw each point at once"""
+        from . import rectify
+        kw.setdefault("device", self._device)
+        return rectify.triangulateMulti(self.cameras(), self.T, uv, seen, **kw)
+
 
 def rigCalibrate(detections, cameras, maxIters=50, device=0):
     """The rigs between N KNOWN cameras, 2 <= N <= 8. cameras[c] = (distortionType, A (3,3), k); detections[c]: a list of

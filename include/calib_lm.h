@@ -513,6 +513,48 @@ int calib_triangulate(int model_a, const double* Aa, const double* ka, int model
                       const double* R, const double* t, int64_t n, const double* uv_a, const double* uv_b, double* out_X,
                       double* out_sse, int32_t* out_status, int device_id);
 
+/* ---- N-view triangulation: one point from every camera of a rig that saw it ----------------------------------------
+ * calib_triangulate for N cameras, 2 <= N <= CALIB_RIG_MAX_CAMERAS, and a per-point mask of the cameras that saw the
+ * point. Camera c is (model, A, k) as above and a rigid transform X_c = R_c X + t_c (R (3,3) row-major, NULL = identity;
+ * t (3), NULL = 0) from the frame in which X is wanted -- camera 0's with the transforms of a rig calibration. No camera
+ * is special: every one goes through its R_c, t_c. uv (N,n,2) is camera-major: the pixel of point i in camera c is at
+ * uv[2 (c n + i)]. seen (n) or NULL: bit c of seen[i] is set where camera c saw point i; NULL = every camera saw every
+ * point. An unseen camera contributes nothing to the point: its pixel is never read, whatever it holds.
+ *   inverse  every seen pixel is inverted as calib_undistort_points does (the same ideal normalised point, bit for bit).
+ *   start    the point closest in least squares to the seen rays o_c + s d_c, o_c = -R_c^T t_c, d_c = R_c^T (x_c, y_c, 1):
+ *            sum_c (I - d_c d_c^T / |d_c|^2) (X - o_c) = 0, a 3 x 3 Cholesky. Two rays: the midpoint of their common
+ *            perpendicular, calib_triangulate's start.
+ *   refine   calib_triangulate's loop on the 2 m PIXEL residuals uv_c - project_c(R_c X + t_c) of the m seen cameras: at
+ *            most 20 damped Gauss-Newton steps, lambda from 1e-3, / 10 on an accepted step, * 10 on a rejected one, the
+ *            same accept rule with eta = 2^-44 max(1, |uv|_inf) over the seen pixels and flat = eta (2 sqrt(error) + eta),
+ *            a candidate must lie in front of EVERY seen camera, a point leaves the loop at a step <= 1e-14 |X|. J^T J,
+ *            J^T r and the error are summed over the seen cameras in index order.
+ *   out_X (n,3); out_sse (n) or NULL: the 2 m residuals squared and summed at X; out_status (n) or NULL, per point the
+ *   first that applies:
+ *     4  fewer than two cameras saw the point
+ *     1  a seen pixel has no inverse in its camera (calib_undistort_points' status 1), or is not finite
+ *     2  degenerate geometry: the largest sin^2 of the angle between any two seen rays is < 1e-12 (N = 2:
+ *        calib_triangulate's rule), or the start's 3 x 3 system is not positive definite, or the start point or the end
+ *        point has Z <= 0 in a seen camera, or the damped 3 x 3 system has a pivot that is not positive
+ *     3  the last accepted step was still > 1e-9 |X|
+ *     0  ok
+ *   out_cov (n,6) or NULL: the lower triangle, in the order 00 10 11 20 21 22, of the UNDAMPED (J^T J)^-1 at the returned
+ *     X -- the covariance of X for unit pixel variance; NaN where a pivot is not positive (the status stays as it is).
+ *   out_res (N,n,2) or NULL, camera-major like uv: the residuals at X, NaN for an unseen camera.
+ *   out_X, out_sse, out_cov and out_res are NaN wherever the status is not 0; the call itself still returns CALIB_OK.
+ *   Which optional outputs are requested does not change a bit of the others.
+ * Stateless, host pointers. CALIB_E_INVALID before any device call: N outside [2, 8], a NULL cameras, A, k, uv or out_X, a
+ * bad model id, alpha or beta equal to 0, |det R_c - 1| > 1e-6, n < 0, a bit of seen at or above N. n == 0 is CALIB_OK
+ * without touching a device. One thread per point, no atomics, no sums across threads: two calls agree bit for bit, and a
+ * point's result does not depend on the cameras that did not see it, nor on how many there are. */
+typedef struct {
+    int model;
+    const double *A, *k, *R, *t;
+} calib_view_camera_t;
+int calib_triangulate_multi(int num_cameras, const calib_view_camera_t* cameras, int64_t n, const double* uv,
+                            const uint32_t* seen, double* out_X, double* out_sse, int32_t* out_status, double* out_cov,
+                            double* out_res, int device_id);
+
 #ifdef __cplusplus
 }
 #endif
