@@ -59,6 +59,7 @@ class ViewCamera(ctypes.Structure):
 
 
 _c_uint32_p = ctypes.POINTER(ctypes.c_uint32)
+_c_uint64_p = ctypes.POINTER(ctypes.c_uint64)
 
 # name -> (restype, argtypes); must list every symbol include/calib_lm.h declares
 SIGNATURES = {
@@ -160,6 +161,13 @@ SIGNATURES = {
     "calib_refine_rig": (ctypes.c_int, [_rig_p, _c_double_p, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                         ctypes.c_double, ctypes.c_double, _c_double_p, _c_double_p, _c_int_p, _c_double_p,
                                         ctypes.c_int]),
+    "calib_rig_joint_normal_eq": (ctypes.c_int, [_rig_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+                                                 _c_double_p, ctypes.c_int]),
+    "calib_rig_joint_step_delta": (ctypes.c_int, [_rig_p, _c_double_p, _c_uint64_p, ctypes.c_double, _c_double_p,
+                                                  ctypes.c_int]),
+    "calib_refine_rig_joint": (ctypes.c_int, [_rig_p, _c_double_p, _c_uint64_p, ctypes.c_int, ctypes.c_double,
+                                              ctypes.c_double, ctypes.c_double, ctypes.c_double, _c_double_p, _c_double_p,
+                                              _c_int_p, _c_double_p, ctypes.c_int]),
     "calib_rectify_maps": (ctypes.c_int, [ctypes.c_int, _c_double_p, _c_double_p, _c_double_p, _c_double_p, ctypes.c_int,
                                           ctypes.c_int, _c_float_p, _c_float_p, ctypes.c_int]),
     "calib_rectify_points": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p,

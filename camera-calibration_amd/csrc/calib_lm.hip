@@ -6,6 +6,7 @@
 #include "stereo.hpp"
 #include "stereo_joint.hpp"
 #include "rig.hpp"
+#include "rig_joint.hpp"
 #include "rectify.hpp"
 #include "triangulate_multi.hpp"
 #include "host_rows.hpp"
@@ -878,7 +879,7 @@ bool shared_covariance(const double* red, int L, uint32_t fixed_mask, double sig
 // ============================================================================ C-ABI
 extern "C" {
 
-int calib_version(void) { return 480; }   // 4.8: calib_triangulate_multi
+int calib_version(void) { return 490; }   // 4.9: calib_rig_joint_*, calib_refine_rig_joint
 
 const char* calib_last_error(void) { return g_err.c_str(); }
 
@@ -2067,20 +2068,22 @@ int calib_remap(int dtype, const void* src, int src_h, int src_w, int channels, 
 
 // ---- stereo calibration: the host side of the LM loop the solvers share (stereo_loop.hpp), then the rig-only solver
 // ---- with both cameras known (stereo.hpp); the joint solver's own part follows the rectification section, the
-// ---- multi-camera rig's (rig.hpp) the joint solver's
+// ---- multi-camera rig's (rig.hpp) the joint solver's, the joint rig's (rig_joint.hpp) ends the file
 namespace {
 
 struct StereoRun;
 
 // What differs between the solvers on the host: the sizes of a problem's buffers and the launches of a round.
 struct StereoSolver {
-    int S;                  // shared unknowns: the rig's 6, LA + LB + 6, or 6 (N - 1)
+    int S;                  // shared unknowns: the rig's 6, LA + LB + 6, 6 (N - 1), or sum L_c + 6 (N - 1)
     int record;             // doubles per view record
     int ntot, nschur;       // entries per workgroup partial of the blocks / of the Schur kernel
-    int views_a;            // views per workgroup of the blocks kernel (the Schur kernel: 16)
+    int views_a;            // views per workgroup of the blocks kernel
     int (*evaluate)(const StereoRun&);      // blocks at the candidate, then its totals and the decision
     int (*step)(const StereoRun&);          // at the accepted point: Schur complement, shared solve, back-substitution
     int (*singular)();                      // the solver's CALIB_E_SINGULAR
+    int views_c = 16;                       // views per workgroup pass of the Schur kernel
+    int grid_a = 0, grid_c = 0;             // > 0: the blocks / Schur kernel's grid loops over its views, at most so many partials
 };
 StereoSolver rig_solver();
 StereoSolver joint_solver(int model_a, int model_b);
@@ -2130,6 +2133,9 @@ struct StereoRun {
     StereoSolver sv{};
     Cam cam[CALIB_RIG_MAX_CAMERAS];
     DevBuf<double> P[2], rec[2], partA[2], tot, partC, delta, trace;
+    DevBuf<double> dshq;                    // the joint rig solver's shared step (StereoState::dsh holds kJMaxS entries)
+    RigJointDesc rj{};                      // its layout, filled once per call
+    uint64_t rjFixed[2] = {0, 0};           // its mask over all S shared unknowns
     DevBuf<StereoState> st;
     DoneWord done;
     int64_t M = 0;
@@ -2172,6 +2178,8 @@ struct StereoRun {
         M = num_views;
         nwgA = (int)((M + sv.views_a - 1) / sv.views_a);
         nwgC = (int)((M + 15) / 16);
+        if (sv.grid_a) nwgA = std::min(nwgA, sv.grid_a);
+        if (sv.grid_c) nwgC = std::min((int)((M + sv.views_c - 1) / sv.views_c), sv.grid_c);
         const size_t K = params();
         for (int s = 0; s < 2; ++s) {
             HIP_TRY(P[s].alloc(K));
@@ -2886,6 +2894,173 @@ int calib_triangulate_multi(int num_cameras, const calib_view_camera_t* cameras,
     if (out_cov) HIP_TRY(hipMemcpy(out_cov, dcov.p, cnt * 48, hipMemcpyDeviceToHost));
     if (out_res) HIP_TRY(hipMemcpy(out_res, dres.p, N * cnt * 16, hipMemcpyDeviceToHost));
     return CALIB_OK;
+}
+
+}  // extern "C"
+
+// ---- joint rig calibration: N cameras, their rigs and the poses in one problem (rig_joint.hpp); the loop is the stereo
+// ---- section's
+namespace {
+
+static_assert(kRjMaxS == 16 * CALIB_RIG_MAX_CAMERAS - 6, "eight radtan cameras");
+
+// S, the per-camera offsets, the slots of the totals and the record stride of a joint rig call
+RigJointDesc rig_joint_layout(const calib_rig_problem_t* p) {
+    RigJointDesc y{};
+    y.nc = p->num_cameras;
+    int s = 0, b = 0;
+    for (int c = 0; c < y.nc; ++c) {
+        y.model[c] = p->cameras[c].model;
+        y.L[c] = 5 + num_distortion(y.model[c]);
+        y.off[c] = s;
+        y.bo[c] = b;
+        const int w = y.width(c);
+        s += w;
+        b += w * (w + 1) / 2;
+    }
+    y.S = s;
+    y.kG = b; y.kErr = b + s; y.kTot = y.kErr + y.nc;
+    y.kGv = 21 + 6 * s; y.kRec = y.kGv + 6; y.kStride = (y.kRec + 7) / 8 * 8;
+    y.kEg = s * (s + 1) / 2; y.kFail = y.kEg + s; y.kSchur = y.kFail + 1;
+    return y;
+}
+
+RigJointArgs rig_joint_args(const StereoRun& r) {
+    RigJointArgs a{};
+    a.d = r.rj;
+    for (int c = 0; c < r.ncam; ++c) a.cam[c] = r.cam[c].view();
+    a.dsh = r.dshq.p;
+    a.fixed[0] = r.rjFixed[0]; a.fixed[1] = r.rjFixed[1];
+    return a;
+}
+
+int rig_joint_evaluate(const StereoRun& r) {
+    const RigJointArgs a = rig_joint_args(r);
+    const StereoBufs bf = r.bufs;
+    hipLaunchKernelGGL(rig_joint_blocks_kernel<kRigMaxCams>, dim3((unsigned)r.nwgA), dim3(64 * kRjWaves), 0, 0, a, bf);
+    LAUNCHED(kNoHandle, "rig_joint_blocks_kernel");
+    hipLaunchKernelGGL(rig_joint_decide_kernel<kRigMaxCams>, dim3(1), dim3(256), 0, 0, a, bf, r.nwgA);
+    LAUNCHED(kNoHandle, "rig_joint_decide_kernel");
+    return CALIB_OK;
+}
+
+int rig_joint_step(const StereoRun& r) {
+    const RigJointArgs a = rig_joint_args(r);
+    const StereoBufs bf = r.bufs;
+    hipLaunchKernelGGL(rig_joint_schur_kernel<kRigMaxCams>, dim3((unsigned)r.nwgC), dim3(256), 0, 0, a, bf);
+    LAUNCHED(kNoHandle, "rig_joint_schur_kernel");
+    hipLaunchKernelGGL(rig_joint_solve_kernel<kRigMaxCams>, dim3(1), dim3(256), 0, 0, a, bf, r.nwgC);
+    LAUNCHED(kNoHandle, "rig_joint_solve_kernel");
+    hipLaunchKernelGGL(rig_joint_backsub_kernel<kRigMaxCams>, dim3((unsigned)((r.M + 63) / 64)), dim3(64), 0, 0, a, bf);
+    LAUNCHED(kNoHandle, "rig_joint_backsub_kernel");
+    return CALIB_OK;
+}
+
+int rig_joint_singular() {
+    return fail(CALIB_E_SINGULAR, "joint rig normal equations singular: a view with fewer than three points over all "
+                                  "cameras, or a pivot of a view block or of the reduced system that is not positive (a "
+                                  "free parameter that no point constrains, such as a free camera that sees nothing)");
+}
+
+// what calib_refine_rig rejects, but for the cameras' shared vectors, which travel in Pq; and a mask bit at or above S
+int check_rig_joint(const calib_rig_problem_t* p, const double* P, const uint64_t* fixed_mask) {
+    if (!p || !P || !p->cameras) return fail(CALIB_E_INVALID, "null argument");
+    if (p->num_cameras < 2 || p->num_cameras > CALIB_RIG_MAX_CAMERAS) return fail(CALIB_E_INVALID, "a rig has 2 to 8 cameras");
+    if (p->num_views < 1) return fail(CALIB_E_INVALID, "rig calibration needs at least one view");
+    int S = 6 * (p->num_cameras - 1);
+    for (int c = 0; c < p->num_cameras; ++c) {
+        const calib_rig_camera_t& cm = p->cameras[c];
+        if (!known_model(cm.model)) return fail(CALIB_E_INVALID, "unknown distortion model");
+        S += 5 + num_distortion(cm.model);
+        const int rc = check_views(p->num_views, cm.offs, cm.uv, cm.xyz);
+        if (rc) return rc;
+    }
+    if (fixed_mask) {
+        const uint64_t hi = S >= 128 ? 0 : (S >= 64 ? fixed_mask[1] >> (S - 64) : fixed_mask[1]);
+        const uint64_t lo = S >= 64 ? 0 : fixed_mask[0] >> S;
+        if (hi || lo) return fail(CALIB_E_INVALID, "fixed_mask has a bit at or above the number of shared unknowns");
+    }
+    return CALIB_OK;
+}
+
+// checks, device, the cameras and the run's buffers with Pq as the start point
+int rig_joint_begin(StereoRun& run, const calib_rig_problem_t* p, const double* P, const uint64_t* fixed_mask, int max_iters,
+                    double lam, double lam_min, double lam_max, double err_min, bool want_trace, bool want_notify,
+                    int device_id) {
+    int rc = check_rig_joint(p, P, fixed_mask);
+    if (rc) return rc;
+    rc = use_device(device_id);
+    if (rc) return rc;
+    run.ncam = p->num_cameras;
+    for (int c = 0; c < p->num_cameras; ++c) {
+        const calib_rig_camera_t& cm = p->cameras[c];
+        rc = run.upload_cam(c, cm.model, p->num_views, cm.offs, cm.uv, cm.xyz, nullptr);
+        if (rc) return rc;
+    }
+    run.rj = rig_joint_layout(p);
+    if (fixed_mask) { run.rjFixed[0] = fixed_mask[0]; run.rjFixed[1] = fixed_mask[1]; }
+    const RigJointDesc& y = run.rj;
+    HIP_TRY(run.dshq.alloc((size_t)y.S));
+    HIP_TRY(hipMemset(run.dshq.p, 0, (size_t)y.S * 8));
+    StereoSolver sv{y.S, y.kStride, y.kTot, y.kSchur, kRjWaves, rig_joint_evaluate, rig_joint_step, rig_joint_singular};
+    sv.views_c = kRjSchurViews;
+    sv.grid_a = kRjBlocksGrid;
+    sv.grid_c = kRjSchurGrid;
+    return run.begin(sv, p->num_views, P, 0, max_iters, lam, lam_min, lam_max, err_min, want_trace, want_notify);
+}
+
+}  // namespace
+
+extern "C" {
+
+int calib_rig_joint_normal_eq(const calib_rig_problem_t* problem, const double* Pq, double* out_B, double* out_E,
+                              double* out_V, double* out_g, double* out_sse_cam, int device_id) {
+    StereoRun run;
+    std::vector<double> rec, tot;
+    int rc = rig_joint_begin(run, problem, Pq, nullptr, 1, 0.0, 0.0, 0.0, 0.0, false, false, device_id);
+    if (rc) return rc;
+    rc = run_blocks(run, rec, tot);
+    if (rc) return rc;
+    const RigJointDesc& y = run.rj;
+    const size_t M = (size_t)problem->num_views, S = (size_t)y.S;
+    if (out_B) {                                            // dense, with its zeros
+        std::fill(out_B, out_B + S * S, 0.0);
+        for (int c = 0; c < y.nc; ++c) {
+            const int w = y.width(c);
+            for (int r = 0; r < w; ++r)
+                for (int q = 0; q <= r; ++q) {
+                    const double v = tot[(size_t)(y.bo[c] + r * (r + 1) / 2 + q)];
+                    out_B[(size_t)(y.off[c] + r) * S + (size_t)(y.off[c] + q)] = v;
+                    out_B[(size_t)(y.off[c] + q) * S + (size_t)(y.off[c] + r)] = v;
+                }
+        }
+    }
+    if (out_g) std::copy(tot.begin() + y.kG, tot.begin() + y.kG + y.S, out_g);
+    if (out_sse_cam) std::copy(tot.begin() + y.kErr, tot.begin() + y.kTot, out_sse_cam);
+    for (size_t v = 0; v < M; ++v) {
+        const double* r = rec.data() + v * (size_t)y.kStride;
+        if (out_V) sym6(r, out_V + v * 36);
+        if (out_E) std::copy(r + 21, r + 21 + 6 * S, out_E + v * 6 * S);
+        if (out_g) std::copy(r + y.kGv, r + y.kGv + 6, out_g + S + v * 6);
+    }
+    return CALIB_OK;
+}
+
+int calib_rig_joint_step_delta(const calib_rig_problem_t* problem, const double* Pq, const uint64_t* fixed_mask,
+                               double lambda, double* out_delta, int device_id) {
+    StereoRun run;
+    const int rc = rig_joint_begin(run, problem, Pq, fixed_mask, 1, lambda, 0.0, 0.0, 0.0, false, false, device_id);
+    return rc ? rc : run_step_delta(run, out_delta);
+}
+
+int calib_refine_rig_joint(const calib_rig_problem_t* problem, double* Pq_inout, const uint64_t* fixed_mask, int max_iters,
+                           double lam_init, double lam_min, double lam_max, double err_min, double* out_sse,
+                           double* out_sse_cam, int* out_iters, double* out_trace, int device_id) {
+    if (max_iters <= 0) return fail(CALIB_E_INVALID, "max_iters must be >= 1");
+    StereoRun run;
+    const int rc = rig_joint_begin(run, problem, Pq_inout, fixed_mask, max_iters, lam_init, lam_min, lam_max, err_min,
+                                   out_trace != nullptr, true, device_id);
+    return rc ? rc : run_refine(run, Pq_inout, max_iters, out_sse, out_sse_cam, out_iters, out_trace);
 }
 
 }  // extern "C"

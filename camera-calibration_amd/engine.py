@@ -952,6 +952,83 @@ def refineRig(cameras, Pr0, maxIters, lamInit=LAMBDA_INITIAL, lamMin=LAMBDA_MIN,
     return sse.value, Pr, iters.value, trace[:iters.value], cam
 
 
+# ---- joint rig calibration: the cameras free as well (calib_rig_joint_*, csrc/rig_joint.hpp) -------------------------
+def rigJointLayout(modelIds):
+    """model ids of the N cameras -> (S, off (N,), L (N,)): camera c's unknowns start at off[c] in Pq -- shared_c (L[c]),
+    then for c >= 1 rig_c (6)"""
+    L = [NUM_SHARED[m] for m in modelIds]
+    off, s = [], 0
+    for c, l in enumerate(L):
+        off.append(s)
+        s += l + (6 if c else 0)
+    return s, tuple(off), tuple(L)
+
+
+def _rigJoint(cameras, Pq, fixedMask=0):
+    """-> (the C struct, what it points into, M, S, Pq (S + 6 M,), the mask's two words or None). The cameras' own shared
+    vectors are not read by the joint calls: the cameras travel in Pq = (shared_0 | shared_1, rig_1 | .. | pose_0, ..)."""
+    cameras = tuple(cameras)
+    N = len(cameras)
+    if not 2 <= N <= nat.RIG_MAX_CAMERAS:
+        raise ValueError(f"a rig has 2 to {nat.RIG_MAX_CAMERAS} cameras, got {N}")
+    arr = (nat.RigCamera * N)()
+    keep, M = [arr], None
+    for c, (modelId, _, offs, s, m) in enumerate(cameras):
+        if modelId not in NUM_SHARED:
+            raise ValueError(f"camera {c}: unknown distortion model id {modelId!r}")
+        offs, s, m = _packedViews(viewOffsets=offs, sensorPoints=s, modelPoints=m)
+        if M is not None and offs.shape[0] - 1 != M:
+            raise ValueError(f"cameras 0 and {c} have {M} and {offs.shape[0] - 1} views")
+        M = offs.shape[0] - 1
+        keep += [offs, s, m]
+        arr[c] = nat.RigCamera(modelId, nat.i64ptr(offs), nat.dptr(s), nat.dptr(m), None)
+    S = rigJointLayout([cam[0] for cam in cameras])[0]
+    Pq = np.ascontiguousarray(np.asarray(Pq, dtype=np.float64).ravel())
+    if Pq.shape[0] != S + 6 * M:
+        raise ValueError(f"Expected shape ({S + 6 * M},) = ({S} shared, {M} poses), got {Pq.shape}")
+    mask = int(fixedMask)
+    if mask < 0 or mask >> S:
+        raise ValueError(f"fixed mask {mask:#x} has bits outside the {S} shared unknowns")
+    words = (ctypes.c_uint64 * 2)(mask & (2 ** 64 - 1), mask >> 64) if mask else None
+    return nat.RigProblem(N, M, arr), keep, M, S, Pq, words
+
+
+def rigJointNormalEquations(cameras, Pq, device=0):
+    """Block-arrow normal equations of the joint rig problem at Pq -> dict B (S,S) [dense, zero outside the cameras'
+    diagonal blocks], E (M,S,6) [shared row, view column], V (M,6,6), g (S + 6 M,), sseCam (N,)."""
+    prob, keep, M, S, Pq, _ = _rigJoint(cameras, Pq)
+    B, E, V, g = np.empty((S, S)), np.empty((M, S, 6)), np.empty((M, 6, 6)), np.empty(S + 6 * M)
+    cam = np.empty(prob.num_cameras)
+    nat.check(nat.loadLibrary().calib_rig_joint_normal_eq(ctypes.byref(prob), nat.dptr(Pq), nat.dptr(B), nat.dptr(E),
+                                                          nat.dptr(V), nat.dptr(g), nat.dptr(cam), int(device)))
+    return {"B": B, "E": E, "V": V, "g": g, "sseCam": cam}
+
+
+def rigJointStepDelta(cameras, Pq, lam, fixedMask=0, device=0):
+    """delta (S + 6 M,) = the LM step of the joint rig problem at Pq with the shared unknowns of fixedMask (a Python int
+    over all S, rigs included) held, solved on the device."""
+    prob, keep, M, S, Pq, words = _rigJoint(cameras, Pq, fixedMask)
+    delta = np.empty(S + 6 * M)
+    nat.check(nat.loadLibrary().calib_rig_joint_step_delta(ctypes.byref(prob), nat.dptr(Pq), words, float(lam),
+                                                           nat.dptr(delta), int(device)))
+    return delta
+
+
+def refineRigJoint(cameras, Pq0, maxIters, fixedMask=0, lamInit=LAMBDA_INITIAL, lamMin=LAMBDA_MIN, lamMax=LAMBDA_MAX,
+                   errMin=PT_ERROR_MIN, device=0):
+    """The LM loop on Pq -> (sse [pre-update, as the reference returns], Pq, iters, trace (iters, 5 + S), sseCam (N,) at
+    the returned Pq)."""
+    prob, keep, M, S, Pq, words = _rigJoint(cameras, Pq0, fixedMask)
+    Pq = Pq.copy()
+    maxIters = int(maxIters)
+    sse, iters, cam = ctypes.c_double(0.0), ctypes.c_int(0), np.empty(prob.num_cameras)
+    trace = np.zeros((max(maxIters, 1), nat.TRACE_HEADER + S))
+    nat.check(nat.loadLibrary().calib_refine_rig_joint(
+        ctypes.byref(prob), nat.dptr(Pq), words, maxIters, float(lamInit), float(lamMin), float(lamMax), float(errMin),
+        ctypes.byref(sse), nat.dptr(cam), ctypes.byref(iters), nat.dptr(trace), int(device)))
+    return sse.value, Pq, iters.value, trace[:iters.value], cam
+
+
 # ---- using a calibrated rig (calib_rectify_*, calib_triangulate, csrc/rectify.hpp): arguments are checked first --------
 def _rotation(R, name="R"):
     if R is None:

@@ -5,13 +5,16 @@ are the N - 1 rigs (rig_c takes camera 0's frame into camera c's, Xc = R_c X0 + 
 frame: ONE set of poses and one covariance tie the cameras together, which N - 1 stereoCalibrate calls pair by pair do
 not give. The start point is host arithmetic on per-view poses (estimatePoses per camera, on the device; a spanning tree
 over the camera pairs that share solved views), the refinement is the LM loop of the reference on the device
-(calib_refine_rig, csrc/rig.hpp), the covariance host arithmetic on the blocks of calib_rig_normal_eq.
+(calib_refine_rig, csrc/rig.hpp), the covariance host arithmetic on the blocks of calib_rig_normal_eq. With refineCameras
+the result of that refinement is the start point of the joint one (calib_refine_rig_joint, csrc/rig_joint.hpp): every
+camera's intrinsics and distortion, the rigs and the poses in one problem, and a covariance that counts the cameras'
+uncertainty.
 """
 from collections import deque
 
 import numpy as np
 
-from . import engine
+from . import engine, fixed
 from .main import calibrateCamera
 from .stereo import (RIG_NAMES, _camera, _solvedPoses, _views, averageTransform, invertPoses, jointCovarianceFromBlocks,
                      parametersToPoses, posesToParameters)
@@ -58,11 +61,16 @@ class RigCalibration:
     """Result of rigCalibrate: T (N,4,4) camera 0's frame into camera c's (T[0] = I), W list of (4,4) board in camera 0,
     Pr the parameter vector (rig_1, .., rig_{N-1}, pose_0, ..), sse the error AT the result (= sseCam.sum()), sseCam /
     numPoints / rms (N,) per camera (rms NaN for a camera without points), iters, trace (iters, 5 + S).
-    sseBeforeLastUpdate is what the refinement itself returns, the reference's convention (src/calibrate.py:171)."""
+    sseBeforeLastUpdate is what the refinement itself returns, the reference's convention (src/calibrate.py:171).
+    From a joint run (rigCalibrate(refineCameras=True)): Pq = (shared_0 | shared_1, rig_1 | .. | pose_0, ..) the joint
+    parameter vector, fixedMask (a Python int) over its S shared unknowns, trace (iters, 5 + S) the joint loop's, rigOnly
+    the RigCalibration of the rig-only refinement it continued from; cameras(), rectify, triangulate and triangulateAll
+    use the refined cameras."""
 
-    def __init__(self, sseBeforeLastUpdate, Pr, iters, trace, sseCam, problem, device):
+    def __init__(self, sseBeforeLastUpdate, Pr, iters, trace, sseCam, problem, device, Pq=None, fixedMask=0, rigOnly=None):
         N = len(problem)
         S = 6 * (N - 1)
+        self.Pq, self.fixedMask, self.rigOnly = Pq, fixedMask, rigOnly
         self.Pr, self.iters, self.trace, self.sseBeforeLastUpdate = Pr, iters, trace, sseBeforeLastUpdate
         self.sseCam = np.asarray(sseCam, dtype=np.float64)
         self.sse = float(self.sseCam.sum())
@@ -83,7 +91,13 @@ class RigCalibration:
 
     def covariance(self):
         """Covariance (S,S) of the rig parameters (parameterNames) at the result: sigma^2 S_undamped^-1 with
-        sigma^2 = sse / (2 n - S - 6 M), the units of CalibrationUncertainty."""
+        sigma^2 = sse / (2 n - S - 6 M), the units of CalibrationUncertainty. From a joint run: of the S shared unknowns
+        of the joint problem (jointParameterNames), sigma^2 S_free^-1 with dof = 2 n - (S - |F|) - 6 M; rows and columns
+        of fixed parameters are exact zeros."""
+        if self.Pq is not None:
+            ne = engine.rigJointNormalEquations(self._problem, self.Pq, self._device)
+            return jointCovarianceFromBlocks(ne["B"], ne["E"], ne["V"], float(ne["sseCam"].sum()),
+                                             int(self.numPoints.sum()), self.fixedMask)
         ne = engine.rigNormalEquations(self._problem, self.Pr, self._device)
         return jointCovarianceFromBlocks(ne["B"], ne["E"], ne["V"], float(ne["sseCam"].sum()), int(self.numPoints.sum()))
 
@@ -91,14 +105,23 @@ class RigCalibration:
         """the 6 x 6 block of covariance() of camera c >= 1 (rho_x, rho_y, rho_z in DEGREES, then t)"""
         if not 1 <= c < self.numCameras:
             raise ValueError(f"camera {c!r} has no rig: expected 1 <= c < {self.numCameras}")
+        if self.Pq is not None:
+            _, off, L = engine.rigJointLayout([cam[0] for cam in self._problem])
+            r = slice(off[c] + L[c], off[c] + L[c] + 6)
+            return self.covariance()[r, r].copy()
         return self.covariance()[6 * (c - 1):6 * c, 6 * (c - 1):6 * c].copy()
 
     def parameterNames(self):
         """names of the S rig unknowns: rig1.rx .. rig{N-1}.tz"""
         return tuple(f"rig{c}.{n}" for c in range(1, self.numCameras) for n in RIG_NAMES)
 
+    def jointParameterNames(self):
+        """names of the S shared unknowns of the joint problem: cam0.alpha .. cam0.k.., cam1.alpha .. cam1.k.., rig1.rx ..
+        rig1.tz, cam2.alpha .."""
+        return jointParameterNames([cam[0] for cam in self._problem])
+
     def cameras(self):
-        """the cameras, each (distortionType, A, k) as rigCalibrate took it"""
+        """the cameras, each (distortionType, A, k) as rigCalibrate took it -- from a joint run, as it refined them"""
         names = {v: n for n, v in engine.MODEL_IDS.items()}
         return tuple((names[modelId], np.array([[s[0], s[2], s[3]], [0.0, s[1], s[4]], [0.0, 0.0, 1.0]]), s[5:].copy())
                      for modelId, s in ((c[0], np.asarray(c[1], dtype=np.float64)) for c in self._problem))
@@ -126,10 +149,67 @@ class RigCalibration:
         return rectify.triangulateMulti(self.cameras(), self.T, uv, seen, **kw)
 
 
-def rigCalibrate(detections, cameras, maxIters=50, device=0):
+def jointParameterNames(modelIds):
+    """names of Pq's shared unknowns for cameras of these model ids"""
+    names = []
+    for c, modelId in enumerate(modelIds):
+        names += [f"cam{c}.{n}" for n in fixed.sharedNames(modelId)]
+        if c:
+            names += [f"rig{c}.{n}" for n in RIG_NAMES]
+    return tuple(names)
+
+
+def jointFixed(modelIds, fixedSpecs=None, fixedRigs=()):
+    """fixedSpecs: None, or one Calibrator(fixed=...)-style spec per camera; fixedRigs: the cameras c >= 1 whose rig is
+    held -> (mask, a Python int over the S shared unknowns of Pq, {index into Pq: value})"""
+    N = len(modelIds)
+    _, off, L = engine.rigJointLayout(modelIds)
+    if fixedSpecs is None:
+        fixedSpecs = [None] * N
+    fixedSpecs = list(fixedSpecs)
+    if len(fixedSpecs) != N:
+        raise ValueError(f"expected one fixed spec per camera ({N}), got {len(fixedSpecs)}")
+    mask, values = 0, {}
+    for c, spec in enumerate(fixedSpecs):
+        m, v = fixed.resolveFixed(fixed.sharedNames(modelIds[c]), spec)
+        mask |= m << off[c]
+        values.update({off[c] + i: x for i, x in v.items()})
+    for c in fixedRigs:
+        if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 1 <= c < N:
+            raise ValueError(f"fixedRigs: camera {c!r} has no rig: expected 1 <= c < {N}")
+        mask |= 0x3f << (off[c] + L[c])
+    return mask, values
+
+
+def packJoint(shared, Pr):
+    """the cameras' shared vectors and Pr = (rig_1, .., rig_{N-1}, pose_0, ..) -> Pq, camera-major"""
+    N = len(shared)
+    Pr = np.asarray(Pr, dtype=np.float64).ravel()
+    parts = [np.asarray(shared[0], dtype=np.float64)]
+    for c in range(1, N):
+        parts += [np.asarray(shared[c], dtype=np.float64), Pr[6 * (c - 1):6 * c]]
+    return np.concatenate(parts + [Pr[6 * (N - 1):]])
+
+
+def unpackJoint(modelIds, Pq):
+    """Pq -> (the cameras' shared vectors, Pr)"""
+    S, off, L = engine.rigJointLayout(modelIds)
+    Pq = np.asarray(Pq, dtype=np.float64).ravel()
+    shared = [Pq[off[c]:off[c] + L[c]].copy() for c in range(len(modelIds))]
+    rigs = [Pq[off[c] + L[c]:off[c] + L[c] + 6] for c in range(1, len(modelIds))]
+    return shared, np.concatenate(rigs + [Pq[S:]])
+
+
+def rigCalibrate(detections, cameras, maxIters=50, device=0, refineCameras=False, fixed=None, fixedRigs=()):
     """The rigs between N KNOWN cameras, 2 <= N <= 8. cameras[c] = (distortionType, A (3,3), k); detections[c]: a list of
     length M, entry i a (sensor (n,2), model (n,3)) pair of view i in camera c, or None / empty where the camera did not
-    see the board (the cameras may see different corners). -> RigCalibration."""
+    see the board (the cameras may see different corners). -> RigCalibration.
+    refineCameras=True continues from that result with the cameras free: every camera's intrinsics and distortion, the
+    rigs and the poses refined together. fixed: one Calibrator(fixed=...)-style spec per camera (values of a {name: value}
+    mapping are written into the joint start point); fixedRigs: the cameras c >= 1 whose rig is held there."""
+    fixedSpecs = fixed
+    if not refineCameras and (fixedSpecs is not None or len(tuple(fixedRigs))):
+        raise ValueError("fixed / fixedRigs apply to the joint refinement: pass refineCameras=True")
     if len(detections) != len(cameras) or not 2 <= len(cameras) <= 8:
         raise ValueError(f"expected 2 to 8 cameras and a detection list for each, got {len(cameras)} and {len(detections)}")
     cams = [_camera(cam, c) for c, cam in enumerate(cameras)]
@@ -142,18 +222,30 @@ def rigCalibrate(detections, cameras, maxIters=50, device=0):
     Pr0 = np.concatenate((posesToParameters(T0[1:]).ravel(), posesToParameters(W0).ravel()))
     problem = tuple((cam[1], cam[4]) + engine.packDetections(v) for cam, v in zip(cams, views))
     sse, Pr, iters, trace, sseCam = engine.refineRig(problem, Pr0, maxIters, device=device)
-    return RigCalibration(sse, Pr, iters, trace, sseCam, problem, device)
+    result = RigCalibration(sse, Pr, iters, trace, sseCam, problem, device)
+    if not refineCameras:
+        return result
+    from . import fixed as fixedModule
+    modelIds = [cam[1] for cam in cams]
+    mask, values = jointFixed(modelIds, fixedSpecs, tuple(fixedRigs))
+    Pq0 = fixedModule.applyFixedValues(packJoint([cam[4] for cam in cams], Pr), values)
+    sse, Pq, iters, trace, sseCam = engine.refineRigJoint(problem, Pq0, maxIters, mask, device=device)
+    shared, PrJ = unpackJoint(modelIds, Pq)
+    refined = tuple((p[0], sh) + p[2:] for p, sh in zip(problem, shared))
+    return RigCalibration(sse, PrJ, iters, trace, sseCam, refined, device, Pq=Pq, fixedMask=mask, rigOnly=result)
 
 
-def calibrateRig(detections, types, maxIters, device=0):
+def calibrateRig(detections, types, maxIters, device=0, joint=False):
     """Every camera from scratch, then the rigs: calibrateCamera on each camera's own non-empty views, then rigCalibrate
     with the results held fixed. -> (results, rig), results[c] = (sse, A, W, k) as calibrateCamera returns it (W over that
-    camera's non-empty views, in order)."""
+    camera's non-empty views, in order). joint=True passes refineCameras=True: rig.cameras() then holds the jointly refined
+    (A, k); results stay the mono ones."""
     if len(detections) != len(types):
         raise ValueError(f"expected a distortion type per camera, got {len(types)} for {len(detections)} cameras")
     results = []
     for c, (dets, distortionType) in enumerate(zip(detections, types)):
         own = [v for v in _views(dets, c) if v[0].shape[0] > 0]
         results.append(calibrateCamera(own, distortionType, maxIters, device=device))
-    rig = rigCalibrate(detections, [(t, A, k) for t, (_, A, _, k) in zip(types, results)], maxIters, device)
+    rig = rigCalibrate(detections, [(t, A, k) for t, (_, A, _, k) in zip(types, results)], maxIters, device,
+                       refineCameras=bool(joint))
     return results, rig

@@ -473,6 +473,33 @@ int calib_refine_rig(const calib_rig_problem_t* problem, double* Pr_inout, int m
                      double lam_max, double err_min, double* out_sse, double* out_sse_cam, int* out_iters, double* out_trace,
                      int device_id);
 
+/* ---- joint rig calibration: N cameras, their rigs and the board poses in one problem --------------------------------
+ * calib_refine_rig with the cameras free as well. Unknowns, camera-major: Pq (S + 6 M) = (shared_0[L0] | shared_1[L1],
+ * rig_1[6] | .. | shared_{N-1}, rig_{N-1}[6] | pose_0[6], .., pose_{M-1}[6]), the shared vectors in the order of P (alpha
+ * beta gamma uc vc k..; L = 10 radtan, 9 fisheye), the 6-tuples, frames and residuals as in Pr; S = sum L_c + 6 (N - 1)
+ * <= 122. At N = 2 Pq is calib_refine_stereo_joint's Pj. The problem is calib_rig_problem_t; cameras[c].shared is not
+ * read and may be NULL (the cameras travel in Pq). fixed_mask: two 64-bit words over all S unknowns, rigs included (bit
+ * s of word s / 64 holds unknown s fixed, by the rule of calib_lm_begin's mask: the step is 0 there and the value keeps
+ * its bits), NULL = none. With every camera bit set the problem is calib_refine_rig's. Stateless, host pointers, any
+ * output may be NULL, fixed-order sums (a call is bitwise reproducible). What calib_refine_rig rejects (but a NULL
+ * shared), and a mask bit at or above S, is CALIB_E_INVALID before any device call.
+ *
+ * calib_rig_joint_normal_eq: out_B (S,S) dense, exactly zero outside its diagonal blocks (L0 wide for camera 0, L_c + 6
+ *   for camera c >= 1); out_E (M,S,6), the band of a camera that did not see the view exactly zero; out_V (M,6,6); out_g
+ *   (S + 6 M) in the order of Pq; out_sse_cam (N).
+ * calib_rig_joint_step_delta: delta (S + 6 M), the LM step at Pq through the Schur complement; 0 at fixed unknowns.
+ * calib_refine_rig_joint: the loop of calib_refine_rig on Pq; out_trace rows are CALIB_TRACE_HEADER + S doubles.
+ * CALIB_E_SINGULAR (Pq_inout left as it was): a view with fewer than three points over all cameras, an empty view, a
+ *   pivot of a view block or of the reduced system that is not positive -- a free camera that sees nothing, camera 0
+ *   included; the same problem succeeds with that camera's bits (and for c >= 1 its rig's) set. */
+int calib_rig_joint_normal_eq(const calib_rig_problem_t* problem, const double* Pq, double* out_B, double* out_E,
+                              double* out_V, double* out_g, double* out_sse_cam, int device_id);
+int calib_rig_joint_step_delta(const calib_rig_problem_t* problem, const double* Pq, const uint64_t* fixed_mask /* [2] */,
+                               double lambda, double* out_delta, int device_id);
+int calib_refine_rig_joint(const calib_rig_problem_t* problem, double* Pq_inout, const uint64_t* fixed_mask /* [2] */,
+                           int max_iters, double lam_init, double lam_min, double lam_max, double err_min, double* out_sse,
+                           double* out_sse_cam, int* out_iters, double* out_trace, int device_id);
+
 /* ---- using a calibrated rig: rectify maps, rectified points, triangulation ---------------------------------------
  * Stateless, host pointers, the work runs on device_id; cameras as in the undistortion entries (A (3,3) row-major, k the
  * model's coefficients). R is a (3,3) row-major rotation; |det R - 1| > 1e-6 is CALIB_E_INVALID, as are a bad model id, a
