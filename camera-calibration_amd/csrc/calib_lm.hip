@@ -2066,261 +2066,17 @@ int calib_remap(int dtype, const void* src, int src_h, int src_w, int channels, 
 
 }  // extern "C"
 
-// ---- stereo calibration: the host side of the LM loop the solvers share (stereo_loop.hpp), then the rig-only solver
-// ---- with both cameras known (stereo.hpp); the joint solver's own part follows the rectification section, the
-// ---- multi-camera rig's (rig.hpp) the joint solver's, the joint rig's (rig_joint.hpp) ends the file
+// ---- the four solvers on the LM loop of stereo_loop.hpp: two known cameras (calib_stereo_*), joint stereo
+// ---- (calib_stereo_joint_*), N known cameras (calib_rig_*), the joint rig (calib_rig_joint_*). Their host side is
+// ---- solver_host.hpp, which needs this file's helpers above; what is left here is each solver's two launch functions,
+// ---- the descriptor that names them and, at the end of the file, the twelve entry points. The launch functions stay
+// ---- where they were among the sections that follow: the module emits a kernel template where it is first launched,
+// ---- and a kernel that changes its place changes every label after it (tools/isa_diff.py).
+#include "solver_host.hpp"
+
 namespace {
 
-struct StereoRun;
-
-// What differs between the solvers on the host: the sizes of a problem's buffers and the launches of a round.
-struct StereoSolver {
-    int S;                  // shared unknowns: the rig's 6, LA + LB + 6, 6 (N - 1), or sum L_c + 6 (N - 1)
-    int record;             // doubles per view record
-    int ntot, nschur;       // entries per workgroup partial of the blocks / of the Schur kernel
-    int views_a;            // views per workgroup of the blocks kernel
-    int (*evaluate)(const StereoRun&);      // blocks at the candidate, then its totals and the decision
-    int (*step)(const StereoRun&);          // at the accepted point: Schur complement, shared solve, back-substitution
-    int (*singular)();                      // the solver's CALIB_E_SINGULAR
-    int views_c = 16;                       // views per workgroup pass of the Schur kernel
-    int grid_a = 0, grid_c = 0;             // > 0: the blocks / Schur kernel's grid loops over its views, at most so many partials
-};
-StereoSolver rig_solver();
-StereoSolver joint_solver(int model_a, int model_b);
-int joint_shared(const calib_stereo_problem_t* p) { return 16 + num_distortion(p->model_a) + num_distortion(p->model_b); }
-
-// The rig-only solver reads the cameras from the problem; the joint one has them in P and adds the mask test.
-int check_stereo(const calib_stereo_problem_t* p, const double* P, bool joint, uint64_t fixed_mask) {
-    if (!p || !P) return fail(CALIB_E_INVALID, "null argument");
-    if (!known_model(p->model_a) || !known_model(p->model_b)) return fail(CALIB_E_INVALID, "unknown distortion model");
-    if (p->num_views < 1) return fail(CALIB_E_INVALID, "stereo calibration needs at least one view");
-    if (!joint && (!p->shared_a || !p->shared_b)) return fail(CALIB_E_INVALID, "null argument");
-    if (joint && fixed_mask >> joint_shared(p)) return fail(CALIB_E_INVALID, "fixed_mask has a bit at or above the number of shared unknowns");
-    const int rc = check_views(p->num_views, p->offs_a, p->uv_a, p->xyz_a);
-    return rc ? rc : check_views(p->num_views, p->offs_b, p->uv_b, p->xyz_b);
-}
-
-// A word in pinned memory that the device sets when the loop is over. Best effort: without it (or without its device
-// address) the host looks at the state instead.
-struct DoneWord {
-    int* host = nullptr;
-    int* dev = nullptr;
-    DoneWord() = default;
-    DoneWord(const DoneWord&) = delete;
-    DoneWord& operator=(const DoneWord&) = delete;
-    ~DoneWord() { if (host) (void)hipHostFree(host); }
-    void create() {
-        void* hp = nullptr; void* dp = nullptr;
-        if (hipHostMalloc(&hp, sizeof(int), hipHostMallocMapped) == hipSuccess) {
-            host = static_cast<int*>(hp);
-            *host = 0;
-            if (hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) dev = static_cast<int*>(dp);
-        }
-        (void)hipGetLastError();
-    }
-    bool set() const { return *static_cast<volatile int*>(host) != 0; }
-};
-
-// Device side of one stereo or rig call: the problem's cameras (two, or up to CALIB_RIG_MAX_CAMERAS), the two (point,
-// record, total) buffer sets the loop alternates between, the state. Released with the scope of the entry point.
-struct StereoRun {
-    struct Cam {
-        DevBuf<int64_t> offs;
-        DevBuf<double2> uv;
-        DevBuf<double> xyz, shared;         // shared: a known camera (not the joint solver's)
-        StereoCam view() const { return StereoCam{offs.p, uv.p, xyz.p}; }
-    };
-    StereoSolver sv{};
-    Cam cam[CALIB_RIG_MAX_CAMERAS];
-    DevBuf<double> P[2], rec[2], partA[2], tot, partC, delta, trace;
-    DevBuf<double> dshq;                    // the joint rig solver's shared step (StereoState::dsh holds kJMaxS entries)
-    RigJointDesc rj{};                      // its layout, filled once per call
-    uint64_t rjFixed[2] = {0, 0};           // its mask over all S shared unknowns
-    DevBuf<StereoState> st;
-    DoneWord done;
-    int64_t M = 0;
-    int nwgA = 0, nwgC = 0, ncam = 0, model[CALIB_RIG_MAX_CAMERAS] = {};
-    StereoBufs bufs{};
-
-    size_t params() const { return (size_t)sv.S + 6 * (size_t)M; }
-    size_t trace_width() const { return (size_t)(CALIB_TRACE_HEADER + sv.S); }
-
-    int upload_cam(int index, int model_id, int64_t M, const int64_t* offs, const double* uv, const double* xyz,
-                   const double* shared) {
-        Cam& c = cam[index];
-        model[index] = model_id;
-        const int64_t n = offs[M];
-        const size_t L = 5 + (size_t)num_distortion(model_id);
-        HIP_TRY(c.offs.alloc((size_t)M + 1));
-        HIP_TRY(c.uv.alloc((size_t)std::max<int64_t>(n, 1)));
-        HIP_TRY(c.xyz.alloc((size_t)std::max<int64_t>(n, 1) * 3));
-        HIP_TRY(hipMemcpy(c.offs.p, offs, ((size_t)M + 1) * 8, hipMemcpyHostToDevice));
-        if (n) HIP_TRY(hipMemcpy(c.uv.p, uv, (size_t)n * 16, hipMemcpyHostToDevice));
-        if (n) HIP_TRY(hipMemcpy(c.xyz.p, xyz, (size_t)n * 24, hipMemcpyHostToDevice));
-        if (shared) {
-            HIP_TRY(c.shared.alloc(L));
-            HIP_TRY(hipMemcpy(c.shared.p, shared, L * 8, hipMemcpyHostToDevice));
-        }
-        return CALIB_OK;
-    }
-
-    // the two cameras of a stereo problem
-    int upload(bool joint, const calib_stereo_problem_t* p) {
-        ncam = 2;
-        const int rc = upload_cam(0, p->model_a, p->num_views, p->offs_a, p->uv_a, p->xyz_a, joint ? nullptr : p->shared_a);
-        return rc ? rc : upload_cam(1, p->model_b, p->num_views, p->offs_b, p->uv_b, p->xyz_b, joint ? nullptr : p->shared_b);
-    }
-
-    // After the cameras: the start point goes into buffer 0, which the bootstrap round evaluates as its candidate (cur = 1)
-    int begin(const StereoSolver& solver, int64_t num_views, const double* P0, uint64_t fixed_mask, int max_iters, double lam,
-              double lam_min, double lam_max, double err_min, bool want_trace, bool want_notify) {
-        sv = solver;
-        M = num_views;
-        nwgA = (int)((M + sv.views_a - 1) / sv.views_a);
-        nwgC = (int)((M + 15) / 16);
-        if (sv.grid_a) nwgA = std::min(nwgA, sv.grid_a);
-        if (sv.grid_c) nwgC = std::min((int)((M + sv.views_c - 1) / sv.views_c), sv.grid_c);
-        const size_t K = params();
-        for (int s = 0; s < 2; ++s) {
-            HIP_TRY(P[s].alloc(K));
-            HIP_TRY(rec[s].alloc((size_t)M * sv.record));
-            HIP_TRY(partA[s].alloc((size_t)nwgA * sv.ntot));
-        }
-        HIP_TRY(tot.alloc(2 * (size_t)sv.ntot));
-        HIP_TRY(partC.alloc((size_t)nwgC * sv.nschur));
-        HIP_TRY(delta.alloc(K));
-        HIP_TRY(st.alloc(1));
-        HIP_TRY(hipMemcpy(P[0].p, P0, K * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(P[1].p, P0, K * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemset(tot.p, 0, 2 * (size_t)sv.ntot * 8));
-        if (want_trace) {
-            HIP_TRY(trace.alloc((size_t)max_iters * trace_width()));
-            HIP_TRY(hipMemset(trace.p, 0, (size_t)max_iters * trace_width() * 8));
-        }
-        StereoState s{};
-        s.lam = lam; s.lam_min = lam_min; s.lam_max = lam_max; s.err_min = err_min;
-        s.err_cur = s.last_err = std::nan("");
-        s.fixed = fixed_mask;
-        s.cur = 1; s.max_iters = max_iters;
-        if (want_notify) {
-            done.create();
-            s.notify = done.dev;
-        }
-        HIP_TRY(hipMemcpy(st.p, &s, sizeof s, hipMemcpyHostToDevice));
-        bufs = StereoBufs{{P[0].p, P[1].p}, {rec[0].p, rec[1].p}, {partA[0].p, partA[1].p}, {tot.p, tot.p + sv.ntot},
-                          partC.p, delta.p, trace.p, st.p, M};
-        return CALIB_OK;
-    }
-
-    int state(StereoState& s) const {
-        HIP_TRY(hipMemcpy(&s, st.p, sizeof s, hipMemcpyDeviceToHost));
-        return CALIB_OK;
-    }
-};
-
-// checks, device, solver and the run's buffers with P as the start point
-int stereo_begin(StereoRun& run, bool joint, const calib_stereo_problem_t* p, const double* P, uint64_t fixed_mask,
-                 int max_iters, double lam, double lam_min, double lam_max, double err_min, bool want_trace, bool want_notify,
-                 int device_id) {
-    int rc = check_stereo(p, P, joint, fixed_mask);
-    if (rc) return rc;
-    rc = use_device(device_id);
-    if (rc) return rc;
-    rc = run.upload(joint, p);
-    if (rc) return rc;
-    return run.begin(joint ? joint_solver(p->model_a, p->model_b) : rig_solver(), p->num_views, P, fixed_mask, max_iters, lam,
-                     lam_min, lam_max, err_min, want_trace, want_notify);
-}
-
-// the blocks at P on the host: every view's record and the totals
-int run_blocks(StereoRun& run, std::vector<double>& rec, std::vector<double>& tot) {
-    int rc = run.sv.evaluate(run);
-    if (rc) return rc;
-    rec.resize((size_t)run.M * run.sv.record);
-    tot.resize((size_t)run.sv.ntot);
-    HIP_TRY(hipMemcpy(rec.data(), run.rec[0].p, rec.size() * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(tot.data(), run.tot.p, tot.size() * 8, hipMemcpyDeviceToHost));
-    return CALIB_OK;
-}
-
-int stereo_blocks(StereoRun& run, bool joint, const calib_stereo_problem_t* p, const double* P, int device_id,
-                  std::vector<double>& rec, std::vector<double>& tot) {
-    const int rc = stereo_begin(run, joint, p, P, 0, 1, 0.0, 0.0, 0.0, 0.0, false, false, device_id);
-    return rc ? rc : run_blocks(run, rec, tot);
-}
-
-// a 6 x 6 lower triangle stored row by row -> the full symmetric matrix
-void sym6(const double* t, double* o) {
-    for (int r = 0; r < 6; ++r)
-        for (int c = 0; c <= r; ++c) o[r * 6 + c] = o[c * 6 + r] = t[r * (r + 1) / 2 + c];
-}
-
-// one step from a run begun with lambda
-int run_step_delta(StereoRun& run, double* out_delta) {
-    int rc = run.sv.evaluate(run);
-    if (rc) return rc;
-    rc = run.sv.step(run);
-    if (rc) return rc;
-    StereoState s;
-    rc = run.state(s);
-    if (rc) return rc;
-    if (s.error) return run.sv.singular();
-    if (out_delta) HIP_TRY(hipMemcpy(out_delta, run.delta.p, run.params() * 8, hipMemcpyDeviceToHost));
-    return CALIB_OK;
-}
-
-int stereo_step_delta(bool joint, const calib_stereo_problem_t* p, const double* P, uint64_t fixed_mask, double lambda,
-                      double* out_delta, int device_id) {
-    StereoRun run;
-    const int rc = stereo_begin(run, joint, p, P, fixed_mask, 1, lambda, 0.0, 0.0, 0.0, false, false, device_id);
-    return rc ? rc : run_step_delta(run, out_delta);
-}
-
-// the loop of a run begun with its start point; out_sse_cam: the error per camera at the returned point
-int run_refine(StereoRun& run, double* P_inout, int max_iters, double* out_sse, double* out_sse_cam, int* out_iters,
-               double* out_trace) {
-    int rc;
-    // round 0 evaluates the start point; round r >= 1 decides iteration r - 1. The host runs ahead of the device: the
-    // done word in pinned memory stops the enqueueing (rounds already in the queue return at once); without such a word,
-    // a synchronised look at the state every 8 rounds.
-    StereoState s;
-    for (int r = 0; r <= max_iters; ++r) {
-        rc = run.sv.evaluate(run);
-        if (rc) return rc;
-        rc = run.sv.step(run);
-        if (rc) return rc;
-        if (run.done.host) {
-            if (run.done.set()) break;
-        } else if ((r + 1) % 8 == 0) {
-            rc = run.state(s);
-            if (rc) return rc;
-            if (s.done) break;
-        }
-    }
-    rc = run.state(s);
-    if (rc) return rc;
-    if (s.error) return run.sv.singular();
-    HIP_TRY(hipMemcpy(P_inout, run.P[s.cur].p, run.params() * 8, hipMemcpyDeviceToHost));
-    if (out_sse) *out_sse = s.last_err;
-    if (out_iters) *out_iters = s.iters;
-    if (out_sse_cam)    // the cameras' errors end the totals
-        HIP_TRY(hipMemcpy(out_sse_cam, run.tot.p + (size_t)s.cur * run.sv.ntot + (run.sv.ntot - run.ncam), (size_t)run.ncam * 8,
-                          hipMemcpyDeviceToHost));
-    if (out_trace && s.iters > 0)
-        HIP_TRY(hipMemcpy(out_trace, run.trace.p, (size_t)s.iters * run.trace_width() * 8, hipMemcpyDeviceToHost));
-    return CALIB_OK;
-}
-
-int stereo_refine(bool joint, const calib_stereo_problem_t* p, double* P_inout, uint64_t fixed_mask, int max_iters,
-                  double lam_init, double lam_min, double lam_max, double err_min, double* out_sse, double* out_sse_ab,
-                  int* out_iters, double* out_trace, int device_id) {
-    if (max_iters <= 0) return fail(CALIB_E_INVALID, "max_iters must be >= 1");
-    StereoRun run;
-    const int rc = stereo_begin(run, joint, p, P_inout, fixed_mask, max_iters, lam_init, lam_min, lam_max, err_min,
-                                out_trace != nullptr, true, device_id);
-    return rc ? rc : run_refine(run, P_inout, max_iters, out_sse, out_sse_ab, out_iters, out_trace);
-}
-
+// ---- the rig between two known cameras (stereo.hpp) --------------------------------------------------------------------
 int rig_evaluate(const StereoRun& r) {
     const StereoCam ca = r.cam[0].view(), cb = r.cam[1].view();
     const StereoBufs bf = r.bufs;
@@ -2350,48 +2106,7 @@ int rig_step(const StereoRun& r) {
     return CALIB_OK;
 }
 
-int stereo_singular() {
-    return fail(CALIB_E_SINGULAR, "stereo normal equations singular: a view with fewer than three points in total or a "
-                                  "pivot that is not positive, or a rig that no view with points in camera b constrains");
-}
-
-StereoSolver rig_solver() { return StereoSolver{6, kStRecord, kStTot, kStSchur, 16, rig_evaluate, rig_step, stereo_singular}; }
-
 }  // namespace
-
-extern "C" {
-
-int calib_stereo_normal_eq(const calib_stereo_problem_t* problem, const double* Ps, double* out_B, double* out_E,
-                           double* out_V, double* out_g, double* out_sse_ab, int device_id) {
-    StereoRun run;
-    std::vector<double> rec, tot;
-    const int rc = stereo_blocks(run, false, problem, Ps, device_id, rec, tot);
-    if (rc) return rc;
-    if (out_B) sym6(tot.data(), out_B);
-    if (out_g) std::copy(tot.begin() + 21, tot.begin() + 27, out_g);
-    if (out_sse_ab) { out_sse_ab[0] = tot[27]; out_sse_ab[1] = tot[28]; }
-    for (size_t v = 0; v < (size_t)problem->num_views; ++v) {
-        const double* r = rec.data() + v * kStRecord;
-        if (out_V) sym6(r + kStV, out_V + v * 36);
-        if (out_E) std::copy(r + kStE, r + kStE + 36, out_E + v * 36);
-        if (out_g) std::copy(r + kStGv, r + kStGv + 6, out_g + 6 + v * 6);
-    }
-    return CALIB_OK;
-}
-
-int calib_stereo_step_delta(const calib_stereo_problem_t* problem, const double* Ps, double lambda, double* out_delta,
-                            int device_id) {
-    return stereo_step_delta(false, problem, Ps, 0, lambda, out_delta, device_id);
-}
-
-int calib_refine_stereo(const calib_stereo_problem_t* problem, double* Ps_inout, int max_iters, double lam_init,
-                        double lam_min, double lam_max, double err_min, double* out_sse, double* out_sse_ab,
-                        int* out_iters, double* out_trace, int device_id) {
-    return stereo_refine(false, problem, Ps_inout, 0, max_iters, lam_init, lam_min, lam_max, err_min, out_sse, out_sse_ab,
-                         out_iters, out_trace, device_id);
-}
-
-}  // extern "C"
 
 // ---- using a calibrated rig (rectify.hpp): rectify maps, rectified points, triangulation -------------------------
 namespace {
@@ -2543,9 +2258,9 @@ int calib_triangulate(int model_a, const double* Aa, const double* ka, int model
 
 }  // extern "C"
 
-// ---- joint stereo calibration: both cameras, the rig and the poses (stereo_joint.hpp); the loop is the section's above
 namespace {
 
+// ---- joint stereo: both cameras, the rig and the poses (stereo_joint.hpp) ----------------------------------------------
 // the two models of a joint call as compile-time shared counts
 template <typename F>
 int dispatch_joint(int model_a, int model_b, F&& f) {
@@ -2588,70 +2303,7 @@ int joint_step(const StereoRun& r) {
     });
 }
 
-int stereo_joint_singular() {
-    return fail(CALIB_E_SINGULAR, "joint stereo normal equations singular: a view with fewer than three points in total, or "
-                                  "a pivot of a view block or of the shared system that is not positive (a free parameter "
-                                  "that no point constrains)");
-}
-
-StereoSolver joint_solver(int model_a, int model_b) {
-    StereoSolver sv{};
-    dispatch_joint(model_a, model_b, [&](auto fa, auto fb) -> int {
-        using Y = JointLayout<ModelTraits<decltype(fa)::MODEL>::L, ModelTraits<decltype(fb)::MODEL>::L>;
-        sv = StereoSolver{Y::S, kJRecord, Y::kTot, Y::kSchur, kJWaves, joint_evaluate, joint_step, stereo_joint_singular};
-        return CALIB_OK;
-    });
-    return sv;
-}
-
-}  // namespace
-
-extern "C" {
-
-int calib_stereo_joint_normal_eq(const calib_stereo_problem_t* problem, const double* Pj, double* out_B, double* out_E,
-                                 double* out_V, double* out_g, double* out_sse_ab, int device_id) {
-    StereoRun run;
-    std::vector<double> rec, tot;
-    const int rc = stereo_blocks(run, true, problem, Pj, device_id, rec, tot);
-    if (rc) return rc;
-    const size_t M = (size_t)problem->num_views, S = (size_t)run.sv.S;
-    return dispatch_joint(problem->model_a, problem->model_b, [&](auto fa, auto fb) -> int {
-        using Y = JointLayout<ModelTraits<decltype(fa)::MODEL>::L, ModelTraits<decltype(fb)::MODEL>::L>;
-        if (out_B)
-            for (int r = 0; r < Y::S; ++r)
-                for (int c = 0; c <= r; ++c) {
-                    const int slot = Y::slotB(r, c);
-                    out_B[r * S + c] = out_B[c * S + r] = slot >= 0 ? tot[(size_t)slot] : 0.0;
-                }
-        if (out_g) std::copy(tot.begin() + Y::kG, tot.begin() + Y::kG + Y::S, out_g);
-        if (out_sse_ab) { out_sse_ab[0] = tot[Y::kErr]; out_sse_ab[1] = tot[Y::kErr + 1]; }
-        for (size_t v = 0; v < M; ++v) {
-            const double* r = rec.data() + v * kJRecord;
-            if (out_V) sym6(r + Y::kV, out_V + v * 36);
-            if (out_E) std::copy(r + Y::kE, r + Y::kE + 6 * Y::S, out_E + v * 6 * S);
-            if (out_g) std::copy(r + Y::kGv, r + Y::kGv + 6, out_g + S + v * 6);
-        }
-        return CALIB_OK;
-    });
-}
-
-int calib_stereo_joint_step_delta(const calib_stereo_problem_t* problem, const double* Pj, uint64_t fixed_mask,
-                                  double lambda, double* out_delta, int device_id) {
-    return stereo_step_delta(true, problem, Pj, fixed_mask, lambda, out_delta, device_id);
-}
-
-int calib_refine_stereo_joint(const calib_stereo_problem_t* problem, double* Pj_inout, uint64_t fixed_mask, int max_iters,
-                              double lam_init, double lam_min, double lam_max, double err_min, double* out_sse,
-                              double* out_sse_ab, int* out_iters, double* out_trace, int device_id) {
-    return stereo_refine(true, problem, Pj_inout, fixed_mask, max_iters, lam_init, lam_min, lam_max, err_min, out_sse,
-                         out_sse_ab, out_iters, out_trace, device_id);
-}
-
-}  // extern "C"
-
-// ---- multi-camera rig calibration: N known cameras, one board (rig.hpp); the loop is the stereo section's ------------
-namespace {
-
+// ---- the rig of N known cameras (rig.hpp) ------------------------------------------------------------------------------
 // the number of cameras of a rig call as a compile-time argument
 template <typename F>
 int dispatch_cameras(int n, F&& f) {
@@ -2667,20 +2319,6 @@ int dispatch_cameras(int n, F&& f) {
     return fail(CALIB_E_INVALID, "a rig has 2 to 8 cameras");
 }
 static_assert(CALIB_RIG_MAX_CAMERAS == kRigMaxCams, "the C ABI's camera count is the kernels'");
-
-int check_rig(const calib_rig_problem_t* p, const double* P) {
-    if (!p || !P || !p->cameras) return fail(CALIB_E_INVALID, "null argument");
-    if (p->num_cameras < 2 || p->num_cameras > CALIB_RIG_MAX_CAMERAS) return fail(CALIB_E_INVALID, "a rig has 2 to 8 cameras");
-    if (p->num_views < 1) return fail(CALIB_E_INVALID, "rig calibration needs at least one view");
-    for (int c = 0; c < p->num_cameras; ++c) {
-        const calib_rig_camera_t& cm = p->cameras[c];
-        if (!known_model(cm.model)) return fail(CALIB_E_INVALID, "unknown distortion model");
-        if (!cm.shared) return fail(CALIB_E_INVALID, "null argument");
-        const int rc = check_views(p->num_views, cm.offs, cm.uv, cm.xyz);
-        if (rc) return rc;
-    }
-    return CALIB_OK;
-}
 
 RigCams rig_cams(const StereoRun& r) {
     RigCams rc{};
@@ -2724,93 +2362,7 @@ int multi_step(const StereoRun& r) {
     });
 }
 
-int multi_singular() {
-    return fail(CALIB_E_SINGULAR, "rig normal equations singular: a view with fewer than three points over all cameras, or "
-                                  "a pivot of a view block or of the reduced system that is not positive (a camera other "
-                                  "than camera 0 that sees nothing)");
-}
-
-StereoSolver multi_solver(int num_cameras) {
-    StereoSolver sv{};
-    dispatch_cameras(num_cameras, [&](auto nc) -> int {
-        using Y = RigLayout<decltype(nc)::value>;
-        sv = StereoSolver{Y::S, Y::kStride, Y::kTot, Y::kSchur, 16, multi_evaluate, multi_step, multi_singular};
-        return CALIB_OK;
-    });
-    return sv;
-}
-
-// checks, device, the cameras and the run's buffers with P as the start point
-int multi_begin(StereoRun& run, const calib_rig_problem_t* p, const double* P, int max_iters, double lam, double lam_min,
-                double lam_max, double err_min, bool want_trace, bool want_notify, int device_id) {
-    int rc = check_rig(p, P);
-    if (rc) return rc;
-    rc = use_device(device_id);
-    if (rc) return rc;
-    run.ncam = p->num_cameras;
-    for (int c = 0; c < p->num_cameras; ++c) {
-        const calib_rig_camera_t& cm = p->cameras[c];
-        rc = run.upload_cam(c, cm.model, p->num_views, cm.offs, cm.uv, cm.xyz, cm.shared);
-        if (rc) return rc;
-    }
-    return run.begin(multi_solver(p->num_cameras), p->num_views, P, 0, max_iters, lam, lam_min, lam_max, err_min, want_trace,
-                     want_notify);
-}
-
 }  // namespace
-
-extern "C" {
-
-int calib_rig_normal_eq(const calib_rig_problem_t* problem, const double* Pr, double* out_B, double* out_E, double* out_V,
-                        double* out_g, double* out_sse_cam, int device_id) {
-    StereoRun run;
-    std::vector<double> rec, tot;
-    int rc = multi_begin(run, problem, Pr, 1, 0.0, 0.0, 0.0, 0.0, false, false, device_id);
-    if (rc) return rc;
-    rc = run_blocks(run, rec, tot);
-    if (rc) return rc;
-    const size_t M = (size_t)problem->num_views, S = (size_t)run.sv.S;
-    return dispatch_cameras(problem->num_cameras, [&](auto nc) -> int {
-        using Y = RigLayout<decltype(nc)::value>;
-        if (out_B)
-            for (int r = 0; r < Y::S; ++r)
-                for (int c = 0; c <= r; ++c) {
-                    const int slot = Y::slotB(r, c);
-                    out_B[r * S + c] = out_B[c * S + r] = slot >= 0 ? tot[(size_t)slot] : 0.0;
-                }
-        for (int c = 1; c < decltype(nc)::value; ++c) {
-            const double* g = tot.data() + Y::kCam * (c - 1) + 21;
-            if (out_g) std::copy(g, g + 6, out_g + 6 * (c - 1));
-        }
-        if (out_sse_cam) std::copy(tot.begin() + Y::kErr, tot.begin() + Y::kTot, out_sse_cam);
-        for (size_t v = 0; v < M; ++v) {
-            const double* r = rec.data() + v * Y::kStride;
-            if (out_V) sym6(r + Y::kV, out_V + v * 36);
-            if (out_E) std::copy(r + Y::kE, r + Y::kE + 6 * Y::S, out_E + v * 6 * S);
-            if (out_g) std::copy(r + Y::kGv, r + Y::kGv + 6, out_g + S + v * 6);
-        }
-        return CALIB_OK;
-    });
-}
-
-int calib_rig_step_delta(const calib_rig_problem_t* problem, const double* Pr, double lambda, double* out_delta,
-                         int device_id) {
-    StereoRun run;
-    const int rc = multi_begin(run, problem, Pr, 1, lambda, 0.0, 0.0, 0.0, false, false, device_id);
-    return rc ? rc : run_step_delta(run, out_delta);
-}
-
-int calib_refine_rig(const calib_rig_problem_t* problem, double* Pr_inout, int max_iters, double lam_init, double lam_min,
-                     double lam_max, double err_min, double* out_sse, double* out_sse_cam, int* out_iters, double* out_trace,
-                     int device_id) {
-    if (max_iters <= 0) return fail(CALIB_E_INVALID, "max_iters must be >= 1");
-    StereoRun run;
-    const int rc = multi_begin(run, problem, Pr_inout, max_iters, lam_init, lam_min, lam_max, err_min, out_trace != nullptr,
-                               true, device_id);
-    return rc ? rc : run_refine(run, Pr_inout, max_iters, out_sse, out_sse_cam, out_iters, out_trace);
-}
-
-}  // extern "C"
 
 // ---- N-view triangulation: one point from every camera of a rig that saw it (triangulate_multi.hpp) ----------------
 extern "C" {
@@ -2898,39 +2450,17 @@ int calib_triangulate_multi(int num_cameras, const calib_view_camera_t* cameras,
 
 }  // extern "C"
 
-// ---- joint rig calibration: N cameras, their rigs and the poses in one problem (rig_joint.hpp); the loop is the stereo
-// ---- section's
 namespace {
 
+// ---- the joint rig: N cameras, their rigs and the poses in one problem (rig_joint.hpp) ---------------------------------
 static_assert(kRjMaxS == 16 * CALIB_RIG_MAX_CAMERAS - 6, "eight radtan cameras");
-
-// S, the per-camera offsets, the slots of the totals and the record stride of a joint rig call
-RigJointDesc rig_joint_layout(const calib_rig_problem_t* p) {
-    RigJointDesc y{};
-    y.nc = p->num_cameras;
-    int s = 0, b = 0;
-    for (int c = 0; c < y.nc; ++c) {
-        y.model[c] = p->cameras[c].model;
-        y.L[c] = 5 + num_distortion(y.model[c]);
-        y.off[c] = s;
-        y.bo[c] = b;
-        const int w = y.width(c);
-        s += w;
-        b += w * (w + 1) / 2;
-    }
-    y.S = s;
-    y.kG = b; y.kErr = b + s; y.kTot = y.kErr + y.nc;
-    y.kGv = 21 + 6 * s; y.kRec = y.kGv + 6; y.kStride = (y.kRec + 7) / 8 * 8;
-    y.kEg = s * (s + 1) / 2; y.kFail = y.kEg + s; y.kSchur = y.kFail + 1;
-    return y;
-}
 
 RigJointArgs rig_joint_args(const StereoRun& r) {
     RigJointArgs a{};
-    a.d = r.rj;
+    a.d = r.sv.rj;
     for (int c = 0; c < r.ncam; ++c) a.cam[c] = r.cam[c].view();
     a.dsh = r.dshq.p;
-    a.fixed[0] = r.rjFixed[0]; a.fixed[1] = r.rjFixed[1];
+    a.fixed[0] = r.fixed.w[0]; a.fixed[1] = r.fixed.w[1];
     return a;
 }
 
@@ -2956,111 +2486,129 @@ int rig_joint_step(const StereoRun& r) {
     return CALIB_OK;
 }
 
-int rig_joint_singular() {
-    return fail(CALIB_E_SINGULAR, "joint rig normal equations singular: a view with fewer than three points over all "
-                                  "cameras, or a pivot of a view block or of the reduced system that is not positive (a "
-                                  "free parameter that no point constrains, such as a free camera that sees nothing)");
-}
-
-// what calib_refine_rig rejects, but for the cameras' shared vectors, which travel in Pq; and a mask bit at or above S
-int check_rig_joint(const calib_rig_problem_t* p, const double* P, const uint64_t* fixed_mask) {
-    if (!p || !P || !p->cameras) return fail(CALIB_E_INVALID, "null argument");
-    if (p->num_cameras < 2 || p->num_cameras > CALIB_RIG_MAX_CAMERAS) return fail(CALIB_E_INVALID, "a rig has 2 to 8 cameras");
-    if (p->num_views < 1) return fail(CALIB_E_INVALID, "rig calibration needs at least one view");
-    int S = 6 * (p->num_cameras - 1);
-    for (int c = 0; c < p->num_cameras; ++c) {
-        const calib_rig_camera_t& cm = p->cameras[c];
-        if (!known_model(cm.model)) return fail(CALIB_E_INVALID, "unknown distortion model");
-        S += 5 + num_distortion(cm.model);
-        const int rc = check_views(p->num_views, cm.offs, cm.uv, cm.xyz);
-        if (rc) return rc;
+// ---- one descriptor per solver -----------------------------------------------------------------------------------------
+StereoSolver solver_desc(SolverKind kind, const int* model, int num_cameras) {
+    StereoSolver sv{};
+    switch (kind) {
+        case kSolveStereo:
+            sv = StereoSolver{6, kStRecord, kStTot, kStSchur, 16, rig_evaluate, rig_step,
+                              "stereo normal equations singular: a view with fewer than three points in total or a pivot that "
+                              "is not positive, or a rig that no view with points in camera b constrains"};
+            sv.map = stereo_block_map();
+            break;
+        case kSolveStereoJoint:
+            dispatch_joint(model[0], model[1], [&](auto fa, auto fb) -> int {
+                constexpr int LA = ModelTraits<decltype(fa)::MODEL>::L, LB = ModelTraits<decltype(fb)::MODEL>::L;
+                using Y = JointLayout<LA, LB>;
+                sv = StereoSolver{Y::S, kJRecord, Y::kTot, Y::kSchur, kJWaves, joint_evaluate, joint_step,
+                                  "joint stereo normal equations singular: a view with fewer than three points in total, or a "
+                                  "pivot of a view block or of the shared system that is not positive (a free parameter that "
+                                  "no point constrains)"};
+                sv.map = joint_block_map<LA, LB>();
+                return CALIB_OK;
+            });
+            break;
+        case kSolveRig:
+            dispatch_cameras(num_cameras, [&](auto nc) -> int {
+                using Y = RigLayout<decltype(nc)::value>;
+                sv = StereoSolver{Y::S, Y::kStride, Y::kTot, Y::kSchur, 16, multi_evaluate, multi_step,
+                                  "rig normal equations singular: a view with fewer than three points over all cameras, or a "
+                                  "pivot of a view block or of the reduced system that is not positive (a camera other than "
+                                  "camera 0 that sees nothing)"};
+                sv.map = rig_block_map<decltype(nc)::value>();
+                return CALIB_OK;
+            });
+            break;
+        case kSolveRigJoint: {
+            const RigJointDesc y = rig_joint_desc(model, num_cameras);
+            sv = StereoSolver{y.S, y.kStride, y.kTot, y.kSchur, kRjWaves, rig_joint_evaluate, rig_joint_step,
+                              "joint rig normal equations singular: a view with fewer than three points over all cameras, or a "
+                              "pivot of a view block or of the reduced system that is not positive (a free parameter that no "
+                              "point constrains, such as a free camera that sees nothing)"};
+            sv.views_c = kRjSchurViews;
+            sv.grid_a = kRjBlocksGrid;
+            sv.grid_c = kRjSchurGrid;
+            sv.rig_joint = true;
+            sv.rj = y;
+            sv.map = rig_joint_block_map(y);
+            break;
+        }
     }
-    if (fixed_mask) {
-        const uint64_t hi = S >= 128 ? 0 : (S >= 64 ? fixed_mask[1] >> (S - 64) : fixed_mask[1]);
-        const uint64_t lo = S >= 64 ? 0 : fixed_mask[0] >> S;
-        if (hi || lo) return fail(CALIB_E_INVALID, "fixed_mask has a bit at or above the number of shared unknowns");
-    }
-    return CALIB_OK;
-}
-
-// checks, device, the cameras and the run's buffers with Pq as the start point
-int rig_joint_begin(StereoRun& run, const calib_rig_problem_t* p, const double* P, const uint64_t* fixed_mask, int max_iters,
-                    double lam, double lam_min, double lam_max, double err_min, bool want_trace, bool want_notify,
-                    int device_id) {
-    int rc = check_rig_joint(p, P, fixed_mask);
-    if (rc) return rc;
-    rc = use_device(device_id);
-    if (rc) return rc;
-    run.ncam = p->num_cameras;
-    for (int c = 0; c < p->num_cameras; ++c) {
-        const calib_rig_camera_t& cm = p->cameras[c];
-        rc = run.upload_cam(c, cm.model, p->num_views, cm.offs, cm.uv, cm.xyz, nullptr);
-        if (rc) return rc;
-    }
-    run.rj = rig_joint_layout(p);
-    if (fixed_mask) { run.rjFixed[0] = fixed_mask[0]; run.rjFixed[1] = fixed_mask[1]; }
-    const RigJointDesc& y = run.rj;
-    HIP_TRY(run.dshq.alloc((size_t)y.S));
-    HIP_TRY(hipMemset(run.dshq.p, 0, (size_t)y.S * 8));
-    StereoSolver sv{y.S, y.kStride, y.kTot, y.kSchur, kRjWaves, rig_joint_evaluate, rig_joint_step, rig_joint_singular};
-    sv.views_c = kRjSchurViews;
-    sv.grid_a = kRjBlocksGrid;
-    sv.grid_c = kRjSchurGrid;
-    return run.begin(sv, p->num_views, P, 0, max_iters, lam, lam_min, lam_max, err_min, want_trace, want_notify);
+    sv.known_cameras = !solver_is_joint(kind);
+    return sv;
 }
 
 }  // namespace
 
+// ---- the entry points of the four solvers
 extern "C" {
+
+int calib_stereo_normal_eq(const calib_stereo_problem_t* problem, const double* Ps, double* out_B, double* out_E,
+                           double* out_V, double* out_g, double* out_sse_ab, int device_id) {
+    return solver_normal_eq(kSolveStereo, problem, Ps, out_B, out_E, out_V, out_g, out_sse_ab, device_id);
+}
+
+int calib_stereo_step_delta(const calib_stereo_problem_t* problem, const double* Ps, double lambda, double* out_delta,
+                            int device_id) {
+    return solver_step_delta(kSolveStereo, problem, Ps, SolverMask(), lambda, out_delta, device_id);
+}
+
+int calib_refine_stereo(const calib_stereo_problem_t* problem, double* Ps_inout, int max_iters, double lam_init,
+                        double lam_min, double lam_max, double err_min, double* out_sse, double* out_sse_ab,
+                        int* out_iters, double* out_trace, int device_id) {
+    return solver_refine(kSolveStereo, problem, Ps_inout, SolverMask(), max_iters, lam_init, lam_min, lam_max, err_min, out_sse,
+                         out_sse_ab, out_iters, out_trace, device_id);
+}
+
+int calib_stereo_joint_normal_eq(const calib_stereo_problem_t* problem, const double* Pj, double* out_B, double* out_E,
+                                 double* out_V, double* out_g, double* out_sse_ab, int device_id) {
+    return solver_normal_eq(kSolveStereoJoint, problem, Pj, out_B, out_E, out_V, out_g, out_sse_ab, device_id);
+}
+
+int calib_stereo_joint_step_delta(const calib_stereo_problem_t* problem, const double* Pj, uint64_t fixed_mask,
+                                  double lambda, double* out_delta, int device_id) {
+    return solver_step_delta(kSolveStereoJoint, problem, Pj, SolverMask(fixed_mask), lambda, out_delta, device_id);
+}
+
+int calib_refine_stereo_joint(const calib_stereo_problem_t* problem, double* Pj_inout, uint64_t fixed_mask, int max_iters,
+                              double lam_init, double lam_min, double lam_max, double err_min, double* out_sse,
+                              double* out_sse_ab, int* out_iters, double* out_trace, int device_id) {
+    return solver_refine(kSolveStereoJoint, problem, Pj_inout, SolverMask(fixed_mask), max_iters, lam_init, lam_min, lam_max,
+                         err_min, out_sse, out_sse_ab, out_iters, out_trace, device_id);
+}
+
+int calib_rig_normal_eq(const calib_rig_problem_t* problem, const double* Pr, double* out_B, double* out_E, double* out_V,
+                        double* out_g, double* out_sse_cam, int device_id) {
+    return solver_normal_eq(kSolveRig, problem, Pr, out_B, out_E, out_V, out_g, out_sse_cam, device_id);
+}
+
+int calib_rig_step_delta(const calib_rig_problem_t* problem, const double* Pr, double lambda, double* out_delta,
+                         int device_id) {
+    return solver_step_delta(kSolveRig, problem, Pr, SolverMask(), lambda, out_delta, device_id);
+}
+
+int calib_refine_rig(const calib_rig_problem_t* problem, double* Pr_inout, int max_iters, double lam_init, double lam_min,
+                     double lam_max, double err_min, double* out_sse, double* out_sse_cam, int* out_iters, double* out_trace,
+                     int device_id) {
+    return solver_refine(kSolveRig, problem, Pr_inout, SolverMask(), max_iters, lam_init, lam_min, lam_max, err_min, out_sse,
+                         out_sse_cam, out_iters, out_trace, device_id);
+}
 
 int calib_rig_joint_normal_eq(const calib_rig_problem_t* problem, const double* Pq, double* out_B, double* out_E,
                               double* out_V, double* out_g, double* out_sse_cam, int device_id) {
-    StereoRun run;
-    std::vector<double> rec, tot;
-    int rc = rig_joint_begin(run, problem, Pq, nullptr, 1, 0.0, 0.0, 0.0, 0.0, false, false, device_id);
-    if (rc) return rc;
-    rc = run_blocks(run, rec, tot);
-    if (rc) return rc;
-    const RigJointDesc& y = run.rj;
-    const size_t M = (size_t)problem->num_views, S = (size_t)y.S;
-    if (out_B) {                                            // dense, with its zeros
-        std::fill(out_B, out_B + S * S, 0.0);
-        for (int c = 0; c < y.nc; ++c) {
-            const int w = y.width(c);
-            for (int r = 0; r < w; ++r)
-                for (int q = 0; q <= r; ++q) {
-                    const double v = tot[(size_t)(y.bo[c] + r * (r + 1) / 2 + q)];
-                    out_B[(size_t)(y.off[c] + r) * S + (size_t)(y.off[c] + q)] = v;
-                    out_B[(size_t)(y.off[c] + q) * S + (size_t)(y.off[c] + r)] = v;
-                }
-        }
-    }
-    if (out_g) std::copy(tot.begin() + y.kG, tot.begin() + y.kG + y.S, out_g);
-    if (out_sse_cam) std::copy(tot.begin() + y.kErr, tot.begin() + y.kTot, out_sse_cam);
-    for (size_t v = 0; v < M; ++v) {
-        const double* r = rec.data() + v * (size_t)y.kStride;
-        if (out_V) sym6(r, out_V + v * 36);
-        if (out_E) std::copy(r + 21, r + 21 + 6 * S, out_E + v * 6 * S);
-        if (out_g) std::copy(r + y.kGv, r + y.kGv + 6, out_g + S + v * 6);
-    }
-    return CALIB_OK;
+    return solver_normal_eq(kSolveRigJoint, problem, Pq, out_B, out_E, out_V, out_g, out_sse_cam, device_id);
 }
 
 int calib_rig_joint_step_delta(const calib_rig_problem_t* problem, const double* Pq, const uint64_t* fixed_mask,
                                double lambda, double* out_delta, int device_id) {
-    StereoRun run;
-    const int rc = rig_joint_begin(run, problem, Pq, fixed_mask, 1, lambda, 0.0, 0.0, 0.0, false, false, device_id);
-    return rc ? rc : run_step_delta(run, out_delta);
+    return solver_step_delta(kSolveRigJoint, problem, Pq, SolverMask(fixed_mask), lambda, out_delta, device_id);
 }
 
 int calib_refine_rig_joint(const calib_rig_problem_t* problem, double* Pq_inout, const uint64_t* fixed_mask, int max_iters,
                            double lam_init, double lam_min, double lam_max, double err_min, double* out_sse,
                            double* out_sse_cam, int* out_iters, double* out_trace, int device_id) {
-    if (max_iters <= 0) return fail(CALIB_E_INVALID, "max_iters must be >= 1");
-    StereoRun run;
-    const int rc = rig_joint_begin(run, problem, Pq_inout, fixed_mask, max_iters, lam_init, lam_min, lam_max, err_min,
-                                   out_trace != nullptr, true, device_id);
-    return rc ? rc : run_refine(run, Pq_inout, max_iters, out_sse, out_sse_cam, out_iters, out_trace);
+    return solver_refine(kSolveRigJoint, problem, Pq_inout, SolverMask(fixed_mask), max_iters, lam_init, lam_min, lam_max,
+                         err_min, out_sse, out_sse_cam, out_iters, out_trace, device_id);
 }
 
 }  // extern "C"

@@ -767,192 +767,13 @@ def remap(image, mapx, mapy, border=0.0, device=0):
     return out
 
 
-# ---- stereo calibration with both cameras known (calib_stereo_*, csrc/stereo.hpp) -----------------------------------
-def _stereoProblem(cameraA, cameraB):
-    """camera = (modelId, shared (L,), viewOffsets (M+1,), sensorPoints (n,2), modelPoints (n,3)) -> (the C struct, the
-    arrays it points into: keep them alive for the call)"""
-    keep, fields = [], {}
-    M = None
-    for tag, (modelId, shared, offs, s, m) in (("a", cameraA), ("b", cameraB)):
-        if modelId not in NUM_SHARED:
-            raise ValueError(f"camera {tag}: unknown distortion model id {modelId!r}")
-        shared = np.ascontiguousarray(np.asarray(shared, dtype=np.float64).ravel())
-        if shared.shape[0] != NUM_SHARED[modelId]:
-            raise ValueError(f"camera {tag}: expected {NUM_SHARED[modelId]} shared parameters, got {shared.shape[0]}")
-        offs, s, m = _packedViews(viewOffsets=offs, sensorPoints=s, modelPoints=m)
-        if M is not None and offs.shape[0] - 1 != M:
-            raise ValueError(f"the cameras have {M} and {offs.shape[0] - 1} views")
-        M = offs.shape[0] - 1
-        keep += [shared, offs, s, m]
-        fields.update({f"model_{tag}": modelId, f"offs_{tag}": nat.i64ptr(offs), f"uv_{tag}": nat.dptr(s),
-                       f"xyz_{tag}": nat.dptr(m), f"shared_{tag}": nat.dptr(shared)})
-    return nat.StereoProblem(num_views=M, **fields), keep, M
-
-
-def _stereoPs(Ps, M):
-    Ps = np.ascontiguousarray(np.asarray(Ps, dtype=np.float64).ravel())
-    if Ps.shape[0] != 6 + 6 * M:
-        raise ValueError(f"Expected shape ({6 + 6 * M},) = (rig, {M} poses), got {Ps.shape}")
-    return Ps
-
-
-def stereoNormalEquations(cameraA, cameraB, Ps, device=0):
-    """Block-arrow normal equations of the stereo problem at Ps = (rig, pose_0, ..) -> dict B (6,6), E (M,6,6) [rig row,
-    view column], V (M,6,6), g (6 + 6 M,), sseA, sseB. Cameras as _stereoProblem takes them."""
-    prob, keep, M = _stereoProblem(cameraA, cameraB)
-    Ps = _stereoPs(Ps, M)
-    B, E, V, g, ab = np.empty((6, 6)), np.empty((M, 6, 6)), np.empty((M, 6, 6)), np.empty(6 + 6 * M), np.empty(2)
-    nat.check(nat.loadLibrary().calib_stereo_normal_eq(ctypes.byref(prob), nat.dptr(Ps), nat.dptr(B), nat.dptr(E),
-                                                       nat.dptr(V), nat.dptr(g), nat.dptr(ab), int(device)))
-    return {"B": B, "E": E, "V": V, "g": g, "sseA": float(ab[0]), "sseB": float(ab[1])}
-
-
-def stereoStepDelta(cameraA, cameraB, Ps, lam, device=0):
-    """delta (6 + 6 M,) = (J^T J + lam diag J^T J)^-1 J^T r of the stereo problem at Ps, solved on the device."""
-    prob, keep, M = _stereoProblem(cameraA, cameraB)
-    Ps = _stereoPs(Ps, M)
-    delta = np.empty(6 + 6 * M)
-    nat.check(nat.loadLibrary().calib_stereo_step_delta(ctypes.byref(prob), nat.dptr(Ps), float(lam), nat.dptr(delta),
-                                                        int(device)))
-    return delta
-
-
-def refineStereo(cameraA, cameraB, Ps0, maxIters, lamInit=LAMBDA_INITIAL, lamMin=LAMBDA_MIN, lamMax=LAMBDA_MAX,
-                 errMin=PT_ERROR_MIN, device=0):
-    """The LM loop on Ps = (rig, pose_0, ..) with both cameras held fixed -> (sse [pre-update, as the reference
-    returns], Ps, iters, trace (iters, 5 + 6), (sseA, sseB) at the returned Ps)."""
-    prob, keep, M = _stereoProblem(cameraA, cameraB)
-    Ps = _stereoPs(Ps0, M).copy()
-    maxIters = int(maxIters)
-    sse, iters, ab = ctypes.c_double(0.0), ctypes.c_int(0), np.empty(2)
-    trace = np.zeros((max(maxIters, 1), nat.TRACE_HEADER + 6))
-    nat.check(nat.loadLibrary().calib_refine_stereo(
-        ctypes.byref(prob), nat.dptr(Ps), maxIters, float(lamInit), float(lamMin), float(lamMax), float(errMin),
-        ctypes.byref(sse), nat.dptr(ab), ctypes.byref(iters), nat.dptr(trace), int(device)))
-    return sse.value, Ps, iters.value, trace[:iters.value], (float(ab[0]), float(ab[1]))
-
-
-# ---- joint stereo calibration: cameras, rig and poses together (calib_stereo_joint_*, csrc/stereo_joint.hpp) ------------
+# ---- the four solvers on one LM loop (csrc/solver_host.hpp): the rig between two known cameras (calib_stereo_*), joint
+# ---- stereo (calib_stereo_joint_*), the rig of N known cameras (calib_rig_*), the joint rig (calib_rig_joint_*) ---------
 def stereoJointShared(cameraA, cameraB):
-    """S = La + Lb + 6, the number of shared unknowns of the joint problem of two cameras (_stereoProblem's tuples)"""
+    """S = La + Lb + 6, the number of shared unknowns of the joint problem of two cameras (_solverProblem's tuples)"""
     return NUM_SHARED[cameraA[0]] + NUM_SHARED[cameraB[0]] + 6
 
 
-def _stereoJoint(cameraA, cameraB, Pj, fixedMask=0):
-    """-> (the C struct, what it points into, M, S, Pj (S + 6 M,), mask). The cameras' own shared vectors are not read
-    by the joint calls: the cameras travel in Pj = (shared_a, shared_b, rig, pose_0, ..)."""
-    prob, keep, M = _stereoProblem(cameraA, cameraB)
-    S = stereoJointShared(cameraA, cameraB)
-    Pj = np.ascontiguousarray(np.asarray(Pj, dtype=np.float64).ravel())
-    if Pj.shape[0] != S + 6 * M:
-        raise ValueError(f"Expected shape ({S + 6 * M},) = ({S} shared, {M} poses), got {Pj.shape}")
-    mask = int(fixedMask)
-    if mask < 0 or mask >> S:
-        raise ValueError(f"fixed mask {mask:#x} has bits outside the {S} shared unknowns")
-    return prob, keep, M, S, Pj, mask
-
-
-def stereoJointNormalEquations(cameraA, cameraB, Pj, device=0):
-    """Block-arrow normal equations of the joint stereo problem at Pj -> dict B (S,S), E (M,S,6) [shared row, view
-    column], V (M,6,6), g (S + 6 M,), sseA, sseB."""
-    prob, keep, M, S, Pj, _ = _stereoJoint(cameraA, cameraB, Pj)
-    B, E, V, g, ab = np.empty((S, S)), np.empty((M, S, 6)), np.empty((M, 6, 6)), np.empty(S + 6 * M), np.empty(2)
-    nat.check(nat.loadLibrary().calib_stereo_joint_normal_eq(ctypes.byref(prob), nat.dptr(Pj), nat.dptr(B), nat.dptr(E),
-                                                             nat.dptr(V), nat.dptr(g), nat.dptr(ab), int(device)))
-    return {"B": B, "E": E, "V": V, "g": g, "sseA": float(ab[0]), "sseB": float(ab[1])}
-
-
-def stereoJointStepDelta(cameraA, cameraB, Pj, lam, fixedMask=0, device=0):
-    """delta (S + 6 M,) = the LM step of the joint stereo problem at Pj with the shared unknowns of fixedMask held,
-    solved on the device."""
-    prob, keep, M, S, Pj, mask = _stereoJoint(cameraA, cameraB, Pj, fixedMask)
-    delta = np.empty(S + 6 * M)
-    nat.check(nat.loadLibrary().calib_stereo_joint_step_delta(ctypes.byref(prob), nat.dptr(Pj), mask, float(lam),
-                                                              nat.dptr(delta), int(device)))
-    return delta
-
-
-def refineStereoJoint(cameraA, cameraB, Pj0, maxIters, fixedMask=0, lamInit=LAMBDA_INITIAL, lamMin=LAMBDA_MIN,
-                      lamMax=LAMBDA_MAX, errMin=PT_ERROR_MIN, device=0):
-    """The LM loop on Pj = (shared_a, shared_b, rig, pose_0, ..) -> (sse [pre-update, as the reference returns], Pj,
-    iters, trace (iters, 5 + S), (sseA, sseB) at the returned Pj)."""
-    prob, keep, M, S, Pj, mask = _stereoJoint(cameraA, cameraB, Pj0, fixedMask)
-    Pj = Pj.copy()
-    maxIters = int(maxIters)
-    sse, iters, ab = ctypes.c_double(0.0), ctypes.c_int(0), np.empty(2)
-    trace = np.zeros((max(maxIters, 1), nat.TRACE_HEADER + S))
-    nat.check(nat.loadLibrary().calib_refine_stereo_joint(
-        ctypes.byref(prob), nat.dptr(Pj), mask, maxIters, float(lamInit), float(lamMin), float(lamMax), float(errMin),
-        ctypes.byref(sse), nat.dptr(ab), ctypes.byref(iters), nat.dptr(trace), int(device)))
-    return sse.value, Pj, iters.value, trace[:iters.value], (float(ab[0]), float(ab[1]))
-
-
-# ---- multi-camera rig calibration with every camera known (calib_rig_*, csrc/rig.hpp) -------------------------------
-def _rigProblem(cameras, Pr):
-    """cameras: a sequence of 2 to 8 (modelId, shared (L,), viewOffsets (M+1,), sensorPoints (n,2), modelPoints (n,3)),
-    _stereoProblem's tuples -> (the C struct, the arrays it points into: keep them alive for the call, M, S,
-    Pr (S + 6 M,))"""
-    cameras = tuple(cameras)
-    N = len(cameras)
-    if not 2 <= N <= nat.RIG_MAX_CAMERAS:
-        raise ValueError(f"a rig has 2 to {nat.RIG_MAX_CAMERAS} cameras, got {N}")
-    arr = (nat.RigCamera * N)()
-    keep, M = [arr], None
-    for c, (modelId, shared, offs, s, m) in enumerate(cameras):
-        if modelId not in NUM_SHARED:
-            raise ValueError(f"camera {c}: unknown distortion model id {modelId!r}")
-        shared = np.ascontiguousarray(np.asarray(shared, dtype=np.float64).ravel())
-        if shared.shape[0] != NUM_SHARED[modelId]:
-            raise ValueError(f"camera {c}: expected {NUM_SHARED[modelId]} shared parameters, got {shared.shape[0]}")
-        offs, s, m = _packedViews(viewOffsets=offs, sensorPoints=s, modelPoints=m)
-        if M is not None and offs.shape[0] - 1 != M:
-            raise ValueError(f"cameras 0 and {c} have {M} and {offs.shape[0] - 1} views")
-        M = offs.shape[0] - 1
-        keep += [shared, offs, s, m]
-        arr[c] = nat.RigCamera(modelId, nat.i64ptr(offs), nat.dptr(s), nat.dptr(m), nat.dptr(shared))
-    S = 6 * (N - 1)
-    Pr = np.ascontiguousarray(np.asarray(Pr, dtype=np.float64).ravel())
-    if Pr.shape[0] != S + 6 * M:
-        raise ValueError(f"Expected shape ({S + 6 * M},) = ({N - 1} rigs, {M} poses), got {Pr.shape}")
-    return nat.RigProblem(N, M, arr), keep, M, S, Pr
-
-
-def rigNormalEquations(cameras, Pr, device=0):
-    """Block-arrow normal equations of the rig problem at Pr = (rig_1, .., rig_{N-1}, pose_0, ..) -> dict B (S,S), E (M,S,6)
-    [shared row, view column], V (M,6,6), g (S + 6 M,), sseCam (N,)."""
-    prob, keep, M, S, Pr = _rigProblem(cameras, Pr)
-    B, E, V, g = np.empty((S, S)), np.empty((M, S, 6)), np.empty((M, 6, 6)), np.empty(S + 6 * M)
-    cam = np.empty(prob.num_cameras)
-    nat.check(nat.loadLibrary().calib_rig_normal_eq(ctypes.byref(prob), nat.dptr(Pr), nat.dptr(B), nat.dptr(E), nat.dptr(V),
-                                                    nat.dptr(g), nat.dptr(cam), int(device)))
-    return {"B": B, "E": E, "V": V, "g": g, "sseCam": cam}
-
-
-def rigStepDelta(cameras, Pr, lam, device=0):
-    """delta (S + 6 M,) = (J^T J + lam diag J^T J)^-1 J^T r of the rig problem at Pr, solved on the device."""
-    prob, keep, M, S, Pr = _rigProblem(cameras, Pr)
-    delta = np.empty(S + 6 * M)
-    nat.check(nat.loadLibrary().calib_rig_step_delta(ctypes.byref(prob), nat.dptr(Pr), float(lam), nat.dptr(delta),
-                                                     int(device)))
-    return delta
-
-
-def refineRig(cameras, Pr0, maxIters, lamInit=LAMBDA_INITIAL, lamMin=LAMBDA_MIN, lamMax=LAMBDA_MAX, errMin=PT_ERROR_MIN,
-              device=0):
-    """The LM loop on Pr with every camera held fixed -> (sse [pre-update, as the reference returns], Pr, iters,
-    trace (iters, 5 + S), sseCam (N,) at the returned Pr)."""
-    prob, keep, M, S, Pr = _rigProblem(cameras, Pr0)
-    Pr = Pr.copy()
-    maxIters = int(maxIters)
-    sse, iters, cam = ctypes.c_double(0.0), ctypes.c_int(0), np.empty(prob.num_cameras)
-    trace = np.zeros((max(maxIters, 1), nat.TRACE_HEADER + S))
-    nat.check(nat.loadLibrary().calib_refine_rig(
-        ctypes.byref(prob), nat.dptr(Pr), maxIters, float(lamInit), float(lamMin), float(lamMax), float(errMin),
-        ctypes.byref(sse), nat.dptr(cam), ctypes.byref(iters), nat.dptr(trace), int(device)))
-    return sse.value, Pr, iters.value, trace[:iters.value], cam
-
-
-# ---- joint rig calibration: the cameras free as well (calib_rig_joint_*, csrc/rig_joint.hpp) -------------------------
 def rigJointLayout(modelIds):
     """model ids of the N cameras -> (S, off (N,), L (N,)): camera c's unknowns start at off[c] in Pq -- shared_c (L[c]),
     then for c >= 1 rig_c (6)"""
@@ -964,69 +785,193 @@ def rigJointLayout(modelIds):
     return s, tuple(off), tuple(L)
 
 
-def _rigJoint(cameras, Pq, fixedMask=0):
-    """-> (the C struct, what it points into, M, S, Pq (S + 6 M,), the mask's two words or None). The cameras' own shared
-    vectors are not read by the joint calls: the cameras travel in Pq = (shared_0 | shared_1, rig_1 | .. | pose_0, ..)."""
+# kind: (S from the model ids; the C entry points of the normal equations, the step and the loop; how the fixed mask
+# travels: None = the cameras are known and their shared vectors are read, no mask; "int"; "words" = two uint64, NULL for 0).
+# The "stereo" kinds take two cameras in a calib_stereo_problem_t, tag them a and b and return their errors as sseA, sseB;
+# the "rig" kinds take 2 to 8 in a calib_rig_problem_t, number them and return sseCam.
+_SOLVERS = {
+    "stereo": (lambda ids: 6, "calib_stereo_normal_eq", "calib_stereo_step_delta", "calib_refine_stereo", None),
+    "stereoJoint": (lambda ids: NUM_SHARED[ids[0]] + NUM_SHARED[ids[1]] + 6, "calib_stereo_joint_normal_eq",
+                    "calib_stereo_joint_step_delta", "calib_refine_stereo_joint", "int"),
+    "rig": (lambda ids: 6 * (len(ids) - 1), "calib_rig_normal_eq", "calib_rig_step_delta", "calib_refine_rig", None),
+    "rigJoint": (lambda ids: rigJointLayout(ids)[0], "calib_rig_joint_normal_eq", "calib_rig_joint_step_delta",
+                 "calib_refine_rig_joint", "words"),
+}
+
+
+def _solverProblem(kind, cameras, P=None, fixedMask=0):
+    """cameras: (modelId, shared (L,), viewOffsets (M+1,), sensorPoints (n,2), modelPoints (n,3)) each; P = (the S shared
+    unknowns of the kind, pose_0, ..) -> (the C struct, the arrays it points into: keep them alive for the call, M, S,
+    P (S + 6 M,), the mask as the C call takes it). The joint kinds do not read the cameras' own shared vectors: the
+    cameras travel in P. Without P only the cameras are packed and checked."""
+    numShared, _, _, _, maskAs = _SOLVERS[kind]
+    pair, joint = kind.startswith("stereo"), maskAs is not None
     cameras = tuple(cameras)
     N = len(cameras)
-    if not 2 <= N <= nat.RIG_MAX_CAMERAS:
+    if not pair and not 2 <= N <= nat.RIG_MAX_CAMERAS:
         raise ValueError(f"a rig has 2 to {nat.RIG_MAX_CAMERAS} cameras, got {N}")
-    arr = (nat.RigCamera * N)()
-    keep, M = [arr], None
-    for c, (modelId, _, offs, s, m) in enumerate(cameras):
+    tags = "ab" if pair else range(N)
+    keep, packed, M = [], [], None
+    for tag, (modelId, shared, offs, s, m) in zip(tags, cameras):
         if modelId not in NUM_SHARED:
-            raise ValueError(f"camera {c}: unknown distortion model id {modelId!r}")
+            raise ValueError(f"camera {tag}: unknown distortion model id {modelId!r}")
+        if joint:
+            shared = None
+        else:
+            shared = np.ascontiguousarray(np.asarray(shared, dtype=np.float64).ravel())
+            if shared.shape[0] != NUM_SHARED[modelId]:
+                raise ValueError(f"camera {tag}: expected {NUM_SHARED[modelId]} shared parameters, got {shared.shape[0]}")
         offs, s, m = _packedViews(viewOffsets=offs, sensorPoints=s, modelPoints=m)
         if M is not None and offs.shape[0] - 1 != M:
-            raise ValueError(f"cameras 0 and {c} have {M} and {offs.shape[0] - 1} views")
+            raise ValueError(f"cameras {tags[0]} and {tag} have {M} and {offs.shape[0] - 1} views")
         M = offs.shape[0] - 1
-        keep += [offs, s, m]
-        arr[c] = nat.RigCamera(modelId, nat.i64ptr(offs), nat.dptr(s), nat.dptr(m), None)
-    S = rigJointLayout([cam[0] for cam in cameras])[0]
-    Pq = np.ascontiguousarray(np.asarray(Pq, dtype=np.float64).ravel())
-    if Pq.shape[0] != S + 6 * M:
-        raise ValueError(f"Expected shape ({S + 6 * M},) = ({S} shared, {M} poses), got {Pq.shape}")
+        keep += [shared, offs, s, m]
+        packed.append((modelId, nat.i64ptr(offs), nat.dptr(s), nat.dptr(m), nat.dptr(shared)))
+    if pair:
+        names = ("model", "offs", "uv", "xyz", "shared")
+        prob = nat.StereoProblem(num_views=M, **{f"{n}_{t}": v for t, cam in zip(tags, packed) for n, v in zip(names, cam)})
+    else:
+        arr = (nat.RigCamera * N)(*(nat.RigCamera(*cam) for cam in packed))
+        keep.append(arr)
+        prob = nat.RigProblem(N, M, arr)
+    S = numShared([cam[0] for cam in cameras])
+    if P is None:
+        return prob, keep, M, S, None, None
+    P = np.ascontiguousarray(np.asarray(P, dtype=np.float64).ravel())
+    if P.shape[0] != S + 6 * M:
+        what = f"{S} shared" if joint else "rig" if pair else f"{N - 1} rigs"
+        raise ValueError(f"Expected shape ({S + 6 * M},) = ({what}, {M} poses), got {P.shape}")
     mask = int(fixedMask)
     if mask < 0 or mask >> S:
         raise ValueError(f"fixed mask {mask:#x} has bits outside the {S} shared unknowns")
-    words = (ctypes.c_uint64 * 2)(mask & (2 ** 64 - 1), mask >> 64) if mask else None
-    return nat.RigProblem(N, M, arr), keep, M, S, Pq, words
+    if maskAs == "words":
+        mask = (ctypes.c_uint64 * 2)(mask & (2 ** 64 - 1), mask >> 64) if mask else None
+    return prob, keep, M, S, P, mask
+
+
+# the packer under the names and in the shapes the tests' raw C calls take it
+def _stereoProblem(cameraA, cameraB):
+    return _solverProblem("stereo", (cameraA, cameraB))[:3]
+
+
+def _rigProblem(cameras, Pr):
+    return _solverProblem("rig", cameras, Pr)[:5]
+
+
+def _rigJoint(cameras, Pq, fixedMask=0):
+    return _solverProblem("rigJoint", cameras, Pq, fixedMask)
+
+
+def _cameraErrors(kind, cam):
+    return (float(cam[0]), float(cam[1])) if kind.startswith("stereo") else cam
+
+
+def _solverNormalEquations(kind, cameras, P, device):
+    cameras = tuple(cameras)
+    prob, keep, M, S, P, _ = _solverProblem(kind, cameras, P)
+    B, E, V, g = np.empty((S, S)), np.empty((M, S, 6)), np.empty((M, 6, 6)), np.empty(S + 6 * M)
+    cam = np.empty(len(cameras))
+    nat.check(getattr(nat.loadLibrary(), _SOLVERS[kind][1])(ctypes.byref(prob), nat.dptr(P), nat.dptr(B), nat.dptr(E),
+                                                            nat.dptr(V), nat.dptr(g), nat.dptr(cam), int(device)))
+    errors = {"sseA": float(cam[0]), "sseB": float(cam[1])} if kind.startswith("stereo") else {"sseCam": cam}
+    return {"B": B, "E": E, "V": V, "g": g, **errors}
+
+
+def _solverStepDelta(kind, cameras, P, lam, fixedMask, device):
+    prob, keep, M, S, P, mask = _solverProblem(kind, cameras, P, fixedMask)
+    delta = np.empty(S + 6 * M)
+    nat.check(getattr(nat.loadLibrary(), _SOLVERS[kind][2])(
+        ctypes.byref(prob), nat.dptr(P), *([] if _SOLVERS[kind][4] is None else [mask]), float(lam), nat.dptr(delta),
+        int(device)))
+    return delta
+
+
+def _solverRefine(kind, cameras, P0, maxIters, fixedMask, lamInit, lamMin, lamMax, errMin, device):
+    cameras = tuple(cameras)
+    prob, keep, M, S, P, mask = _solverProblem(kind, cameras, P0, fixedMask)
+    P = P.copy()
+    maxIters = int(maxIters)
+    sse, iters, cam = ctypes.c_double(0.0), ctypes.c_int(0), np.empty(len(cameras))
+    trace = np.zeros((max(maxIters, 1), nat.TRACE_HEADER + S))
+    nat.check(getattr(nat.loadLibrary(), _SOLVERS[kind][3])(
+        ctypes.byref(prob), nat.dptr(P), *([] if _SOLVERS[kind][4] is None else [mask]), maxIters, float(lamInit),
+        float(lamMin), float(lamMax), float(errMin), ctypes.byref(sse), nat.dptr(cam), ctypes.byref(iters), nat.dptr(trace),
+        int(device)))
+    return sse.value, P, iters.value, trace[:iters.value], _cameraErrors(kind, cam)
+
+
+def stereoNormalEquations(cameraA, cameraB, Ps, device=0):
+    """Block-arrow normal equations of the stereo problem at Ps = (rig, pose_0, ..) -> dict B (6,6), E (M,6,6) [rig row,
+    view column], V (M,6,6), g (6 + 6 M,), sseA, sseB. Cameras as _solverProblem takes them."""
+    return _solverNormalEquations("stereo", (cameraA, cameraB), Ps, device)
+
+
+def stereoStepDelta(cameraA, cameraB, Ps, lam, device=0):
+    """delta (6 + 6 M,) = (J^T J + lam diag J^T J)^-1 J^T r of the stereo problem at Ps, solved on the device."""
+    return _solverStepDelta("stereo", (cameraA, cameraB), Ps, lam, 0, device)
+
+
+def refineStereo(cameraA, cameraB, Ps0, maxIters, lamInit=LAMBDA_INITIAL, lamMin=LAMBDA_MIN, lamMax=LAMBDA_MAX,
+                 errMin=PT_ERROR_MIN, device=0):
+    """The LM loop on Ps = (rig, pose_0, ..) with both cameras held fixed -> (sse [pre-update, as the reference
+    returns], Ps, iters, trace (iters, 5 + 6), (sseA, sseB) at the returned Ps)."""
+    return _solverRefine("stereo", (cameraA, cameraB), Ps0, maxIters, 0, lamInit, lamMin, lamMax, errMin, device)
+
+
+def stereoJointNormalEquations(cameraA, cameraB, Pj, device=0):
+    """Block-arrow normal equations of the joint stereo problem at Pj -> dict B (S,S), E (M,S,6) [shared row, view
+    column], V (M,6,6), g (S + 6 M,), sseA, sseB."""
+    return _solverNormalEquations("stereoJoint", (cameraA, cameraB), Pj, device)
+
+
+def stereoJointStepDelta(cameraA, cameraB, Pj, lam, fixedMask=0, device=0):
+    """delta (S + 6 M,) = the LM step of the joint stereo problem at Pj with the shared unknowns of fixedMask held,
+    solved on the device."""
+    return _solverStepDelta("stereoJoint", (cameraA, cameraB), Pj, lam, fixedMask, device)
+
+
+def refineStereoJoint(cameraA, cameraB, Pj0, maxIters, fixedMask=0, lamInit=LAMBDA_INITIAL, lamMin=LAMBDA_MIN,
+                      lamMax=LAMBDA_MAX, errMin=PT_ERROR_MIN, device=0):
+    """The LM loop on Pj = (shared_a, shared_b, rig, pose_0, ..) -> (sse [pre-update, as the reference returns], Pj,
+    iters, trace (iters, 5 + S), (sseA, sseB) at the returned Pj)."""
+    return _solverRefine("stereoJoint", (cameraA, cameraB), Pj0, maxIters, fixedMask, lamInit, lamMin, lamMax, errMin, device)
+
+
+def rigNormalEquations(cameras, Pr, device=0):
+    """Block-arrow normal equations of the rig problem at Pr = (rig_1, .., rig_{N-1}, pose_0, ..) -> dict B (S,S), E (M,S,6)
+    [shared row, view column], V (M,6,6), g (S + 6 M,), sseCam (N,)."""
+    return _solverNormalEquations("rig", cameras, Pr, device)
+
+
+def rigStepDelta(cameras, Pr, lam, device=0):
+    """delta (S + 6 M,) = (J^T J + lam diag J^T J)^-1 J^T r of the rig problem at Pr, solved on the device."""
+    return _solverStepDelta("rig", cameras, Pr, lam, 0, device)
+
+
+def refineRig(cameras, Pr0, maxIters, lamInit=LAMBDA_INITIAL, lamMin=LAMBDA_MIN, lamMax=LAMBDA_MAX, errMin=PT_ERROR_MIN,
+              device=0):
+    """The LM loop on Pr with every camera held fixed -> (sse [pre-update, as the reference returns], Pr, iters,
+    trace (iters, 5 + S), sseCam (N,) at the returned Pr)."""
+    return _solverRefine("rig", cameras, Pr0, maxIters, 0, lamInit, lamMin, lamMax, errMin, device)
 
 
 def rigJointNormalEquations(cameras, Pq, device=0):
     """Block-arrow normal equations of the joint rig problem at Pq -> dict B (S,S) [dense, zero outside the cameras'
     diagonal blocks], E (M,S,6) [shared row, view column], V (M,6,6), g (S + 6 M,), sseCam (N,)."""
-    prob, keep, M, S, Pq, _ = _rigJoint(cameras, Pq)
-    B, E, V, g = np.empty((S, S)), np.empty((M, S, 6)), np.empty((M, 6, 6)), np.empty(S + 6 * M)
-    cam = np.empty(prob.num_cameras)
-    nat.check(nat.loadLibrary().calib_rig_joint_normal_eq(ctypes.byref(prob), nat.dptr(Pq), nat.dptr(B), nat.dptr(E),
-                                                          nat.dptr(V), nat.dptr(g), nat.dptr(cam), int(device)))
-    return {"B": B, "E": E, "V": V, "g": g, "sseCam": cam}
+    return _solverNormalEquations("rigJoint", cameras, Pq, device)
 
 
 def rigJointStepDelta(cameras, Pq, lam, fixedMask=0, device=0):
     """delta (S + 6 M,) = the LM step of the joint rig problem at Pq with the shared unknowns of fixedMask (a Python int
     over all S, rigs included) held, solved on the device."""
-    prob, keep, M, S, Pq, words = _rigJoint(cameras, Pq, fixedMask)
-    delta = np.empty(S + 6 * M)
-    nat.check(nat.loadLibrary().calib_rig_joint_step_delta(ctypes.byref(prob), nat.dptr(Pq), words, float(lam),
-                                                           nat.dptr(delta), int(device)))
-    return delta
+    return _solverStepDelta("rigJoint", cameras, Pq, lam, fixedMask, device)
 
 
 def refineRigJoint(cameras, Pq0, maxIters, fixedMask=0, lamInit=LAMBDA_INITIAL, lamMin=LAMBDA_MIN, lamMax=LAMBDA_MAX,
                    errMin=PT_ERROR_MIN, device=0):
     """The LM loop on Pq -> (sse [pre-update, as the reference returns], Pq, iters, trace (iters, 5 + S), sseCam (N,) at
     the returned Pq)."""
-    prob, keep, M, S, Pq, words = _rigJoint(cameras, Pq0, fixedMask)
-    Pq = Pq.copy()
-    maxIters = int(maxIters)
-    sse, iters, cam = ctypes.c_double(0.0), ctypes.c_int(0), np.empty(prob.num_cameras)
-    trace = np.zeros((max(maxIters, 1), nat.TRACE_HEADER + S))
-    nat.check(nat.loadLibrary().calib_refine_rig_joint(
-        ctypes.byref(prob), nat.dptr(Pq), words, maxIters, float(lamInit), float(lamMin), float(lamMax), float(errMin),
-        ctypes.byref(sse), nat.dptr(cam), ctypes.byref(iters), nat.dptr(trace), int(device)))
-    return sse.value, Pq, iters.value, trace[:iters.value], cam
+    return _solverRefine("rigJoint", cameras, Pq0, maxIters, fixedMask, lamInit, lamMin, lamMax, errMin, device)
 
 
 # ---- using a calibrated rig (calib_rectify_*, calib_triangulate, csrc/rectify.hpp): arguments are checked first --------

@@ -16,7 +16,7 @@ import numpy as np
 
 from . import engine, fixed
 from .main import calibrateCamera
-from .stereo import (RIG_NAMES, _camera, _solvedPoses, _views, averageTransform, invertPoses, jointCovarianceFromBlocks,
+from .stereo import (RIG_NAMES, _camera, _solvedPoses, _views, averageTransform, camerasOf, invertPoses, jointCovarianceFromBlocks,
                      parametersToPoses, posesToParameters)
 
 
@@ -122,9 +122,7 @@ class RigCalibration:
 
     def cameras(self):
         """the cameras, each (distortionType, A, k) as rigCalibrate took it -- from a joint run, as it refined them"""
-        names = {v: n for n, v in engine.MODEL_IDS.items()}
-        return tuple((names[modelId], np.array([[s[0], s[2], s[3]], [0.0, s[1], s[4]], [0.0, 0.0, 1.0]]), s[5:].copy())
-                     for modelId, s in ((c[0], np.asarray(c[1], dtype=np.float64)) for c in self._problem))
+        return camerasOf(self._problem)
 
     def rectify(self, a, b, size, **kw):
         """rectify.stereoRectify for the pair (a, b): size = (width, height) of the images -> StereoRectification"""

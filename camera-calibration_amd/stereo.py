@@ -119,15 +119,14 @@ def jointCovarianceFromBlocks(B, E, V, sse, numPoints, fixedMask=0):
 def rigCovarianceFromBlocks(B, E, V, sse, numPoints):
     """sigma^2 S^-1 (6,6; Euler angles in degrees, then t) with S = B - sum_i E_i V_i^-1 E_i^T the undamped Schur
     complement of the view blocks and sigma^2 = sse / (2 numPoints - 6 - 6 M). ValueError when dof <= 0."""
-    B = np.asarray(B, dtype=np.float64).reshape(6, 6)
-    E = np.asarray(E, dtype=np.float64).reshape(-1, 6, 6)
-    V = np.asarray(V, dtype=np.float64).reshape(-1, 6, 6)
-    dof = 2 * int(numPoints) - 6 - 6 * V.shape[0]
-    if dof <= 0:
-        raise ValueError(f"{numPoints} points give {2 * int(numPoints)} equations for {6 + 6 * V.shape[0]} unknowns: no "
-                         "degrees of freedom are left for the covariance")
-    S = B - np.einsum("mij,mjk->ik", E, np.linalg.solve(V, np.transpose(E, (0, 2, 1))))
-    return (sse / dof) * np.linalg.inv(S)
+    return jointCovarianceFromBlocks(np.asarray(B, dtype=np.float64).reshape(6, 6), E, V, sse, numPoints)
+
+
+def camerasOf(problem):
+    """the cameras of an engine problem (tuples that begin with modelId, shared) as (distortionType, A, k) each"""
+    names = {v: n for n, v in engine.MODEL_IDS.items()}
+    return tuple((names[modelId], np.array([[s[0], s[2], s[3]], [0.0, s[1], s[4]], [0.0, 0.0, 1.0]]), s[5:].copy())
+                 for modelId, s in ((c[0], np.asarray(c[1], dtype=np.float64)) for c in problem))
 
 
 class StereoCalibration:
@@ -178,9 +177,7 @@ class StereoCalibration:
 
     def cameras(self):
         """(cameraA, cameraB), each (distortionType, A, k) as stereoCalibrate took it"""
-        names = {v: n for n, v in engine.MODEL_IDS.items()}
-        return tuple((names[modelId], np.array([[s[0], s[2], s[3]], [0.0, s[1], s[4]], [0.0, 0.0, 1.0]]), s[5:].copy())
-                     for modelId, s in ((c[0], np.asarray(c[1], dtype=np.float64)) for c in self._problem))
+        return camerasOf(self._problem)
 
     def rectify(self, size, **kw):
         """rectify.stereoRectify for this rig: size = (width, height) of the images -> StereoRectification"""
