@@ -51,6 +51,15 @@ class RigProblem(ctypes.Structure):
 
 
 _rig_p = ctypes.POINTER(RigProblem)
+LOSS_NONE, LOSS_HUBER, LOSS_CAUCHY = 0, 1, 2
+
+
+class Loss(ctypes.Structure):
+    """calib_loss_t"""
+    _fields_ = [("kind", ctypes.c_int), ("scale", ctypes.c_double)]
+
+
+_loss_p = ctypes.POINTER(Loss)
 
 
 class ViewCamera(ctypes.Structure):
@@ -168,6 +177,14 @@ SIGNATURES = {
     "calib_refine_rig_joint": (ctypes.c_int, [_rig_p, _c_double_p, _c_uint64_p, ctypes.c_int, ctypes.c_double,
                                               ctypes.c_double, ctypes.c_double, ctypes.c_double, _c_double_p, _c_double_p,
                                               _c_int_p, _c_double_p, ctypes.c_int]),
+    "calib_rig_robust_normal_eq": (ctypes.c_int, [_rig_p, _c_double_p, _loss_p, _c_double_p, _c_double_p, _c_double_p,
+                                                  _c_double_p, _c_double_p, ctypes.c_int]),
+    "calib_rig_robust_step_delta": (ctypes.c_int, [_rig_p, _c_double_p, _c_uint64_p, _loss_p, ctypes.c_double, _c_double_p,
+                                                   ctypes.c_int]),
+    "calib_refine_rig_robust": (ctypes.c_int, [_rig_p, _c_double_p, _c_uint64_p, _loss_p, ctypes.c_int, ctypes.c_double,
+                                               ctypes.c_double, ctypes.c_double, ctypes.c_double, _c_double_p, _c_double_p,
+                                               _c_int_p, _c_double_p, ctypes.c_int]),
+    "calib_rig_residuals": (ctypes.c_int, [_rig_p, _c_double_p, _c_double_p, ctypes.c_int]),
     "calib_rectify_maps": (ctypes.c_int, [ctypes.c_int, _c_double_p, _c_double_p, _c_double_p, _c_double_p, ctypes.c_int,
                                           ctypes.c_int, _c_float_p, _c_float_p, ctypes.c_int]),
     "calib_rectify_points": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p,

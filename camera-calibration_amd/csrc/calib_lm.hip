@@ -879,7 +879,7 @@ bool shared_covariance(const double* red, int L, uint32_t fixed_mask, double sig
 // ============================================================================ C-ABI
 extern "C" {
 
-int calib_version(void) { return 490; }   // 4.9: calib_rig_joint_*, calib_refine_rig_joint
+int calib_version(void) { return 500; }   // 5.0: calib_rig_robust_*, calib_refine_rig_robust, calib_rig_residuals
 
 const char* calib_last_error(void) { return g_err.c_str(); }
 
@@ -2486,6 +2486,27 @@ int rig_joint_step(const StereoRun& r) {
     return CALIB_OK;
 }
 
+// the blocks of the problem re-weighted by the run's loss; the decision runs on the sums of rho
+int rig_joint_robust_evaluate(const StereoRun& r) {
+    const RigJointArgs a = rig_joint_args(r);
+    const StereoBufs bf = r.bufs;
+    hipLaunchKernelGGL(rig_joint_robust_blocks_kernel<kRigMaxCams>, dim3((unsigned)r.nwgA), dim3(64 * kRjWaves), 0, 0, a, bf,
+                       r.loss);
+    LAUNCHED(kNoHandle, "rig_joint_robust_blocks_kernel");
+    hipLaunchKernelGGL(rig_joint_decide_kernel<kRigMaxCams>, dim3(1), dim3(256), 0, 0, a, bf, r.nwgA);
+    LAUNCHED(kNoHandle, "rig_joint_decide_kernel");
+    return CALIB_OK;
+}
+
+int rig_joint_residuals(const StereoRun& r, const double* Pq, double* out) {
+    const RigJointArgs a = rig_joint_args(r);
+    const unsigned grid = (unsigned)std::min<int64_t>((r.M + kRjResidualWaves - 1) / kRjResidualWaves, kRjResidualGrid);
+    hipLaunchKernelGGL(rig_residuals_kernel<kRigMaxCams>, dim3(grid), dim3(64 * kRjResidualWaves), 0, 0, a, Pq, r.M,
+                       reinterpret_cast<double2*>(out));
+    LAUNCHED(kNoHandle, "rig_residuals_kernel");
+    return CALIB_OK;
+}
+
 // ---- one descriptor per solver -----------------------------------------------------------------------------------------
 StereoSolver solver_desc(SolverKind kind, const int* model, int num_cameras) {
     StereoSolver sv{};
@@ -2529,6 +2550,8 @@ StereoSolver solver_desc(SolverKind kind, const int* model, int num_cameras) {
             sv.grid_a = kRjBlocksGrid;
             sv.grid_c = kRjSchurGrid;
             sv.rig_joint = true;
+            sv.evaluate_robust = rig_joint_robust_evaluate;
+            sv.residuals = rig_joint_residuals;
             sv.rj = y;
             sv.map = rig_joint_block_map(y);
             break;
@@ -2609,6 +2632,34 @@ int calib_refine_rig_joint(const calib_rig_problem_t* problem, double* Pq_inout,
                            double* out_sse_cam, int* out_iters, double* out_trace, int device_id) {
     return solver_refine(kSolveRigJoint, problem, Pq_inout, SolverMask(fixed_mask), max_iters, lam_init, lam_min, lam_max,
                          err_min, out_sse, out_sse_cam, out_iters, out_trace, device_id);
+}
+
+// robust losses on the joint rig: the same three drivers with the loss in the run; no loss is the plain entry point
+int calib_rig_robust_normal_eq(const calib_rig_problem_t* problem, const double* Pq, const calib_loss_t* loss, double* out_B,
+                               double* out_E, double* out_V, double* out_g, double* out_cost_cam, int device_id) {
+    if (loss_is_plain(loss)) return calib_rig_joint_normal_eq(problem, Pq, out_B, out_E, out_V, out_g, out_cost_cam, device_id);
+    return solver_normal_eq(kSolveRigJoint, problem, Pq, out_B, out_E, out_V, out_g, out_cost_cam, device_id, loss);
+}
+
+int calib_rig_robust_step_delta(const calib_rig_problem_t* problem, const double* Pq, const uint64_t* fixed_mask,
+                                const calib_loss_t* loss, double lambda, double* out_delta, int device_id) {
+    if (loss_is_plain(loss)) return calib_rig_joint_step_delta(problem, Pq, fixed_mask, lambda, out_delta, device_id);
+    return solver_step_delta(kSolveRigJoint, problem, Pq, SolverMask(fixed_mask), lambda, out_delta, device_id, loss);
+}
+
+int calib_refine_rig_robust(const calib_rig_problem_t* problem, double* Pq_inout, const uint64_t* fixed_mask,
+                            const calib_loss_t* loss, int max_iters, double lam_init, double lam_min, double lam_max,
+                            double err_min, double* out_cost, double* out_cost_cam, int* out_iters, double* out_trace,
+                            int device_id) {
+    if (loss_is_plain(loss))
+        return calib_refine_rig_joint(problem, Pq_inout, fixed_mask, max_iters, lam_init, lam_min, lam_max, err_min, out_cost,
+                                      out_cost_cam, out_iters, out_trace, device_id);
+    return solver_refine(kSolveRigJoint, problem, Pq_inout, SolverMask(fixed_mask), max_iters, lam_init, lam_min, lam_max,
+                         err_min, out_cost, out_cost_cam, out_iters, out_trace, device_id, loss);
+}
+
+int calib_rig_residuals(const calib_rig_problem_t* problem, const double* Pq, double* out_res, int device_id) {
+    return solver_residuals(kSolveRigJoint, problem, Pq, out_res, device_id);
 }
 
 }  // extern "C"

@@ -26,6 +26,8 @@
 //                             of B + lam diag B - sum (LDS, 59 KiB), the fixed mask, Cholesky, both substitutions
 //   rig_joint_backsub_kernel  one lane per view (stereo_backsub_kernel with a run-time S, the step and the 128-bit mask in
 //                             this solver's own arguments: StereoState::dsh holds 42 entries and stays as it is)
+// Under a robust loss (the end of this file) rig_joint_robust_blocks_kernel takes the place of the first launch; the
+// other four run unchanged on its totals and records. rig_residuals_kernel writes every point's residual.
 // The buffers, the state and the end of the loop are stereo_loop.hpp's. The kernels need no compile-time argument; they
 // are templates on the largest number of cameras all the same: a template is emitted where it is first launched, at the
 // end of the module, so the module's other kernels keep their place and labels.
@@ -105,6 +107,14 @@ __device__ __forceinline__ void rig_joint_decide(const StereoBufs& bf, int cand,
     if (!(st->lam_min < lam1 && lam1 < st->lam_max) || err0 < st->err_min || it + 1 >= st->max_iters) stereo_stop(st, 0);
 }
 
+// A robust loss of one launch (rig_joint_robust_blocks_kernel): CALIB_LOSS_HUBER or CALIB_LOSS_CAUCHY and its scale delta
+// in pixels. A kernel argument of its own: RigJointArgs and StereoBufs keep their kernarg offsets.
+constexpr int kLossHuber = 1, kLossCauchy = 2;
+struct RigLoss {
+    int kind;
+    double scale;
+};
+
 // the tiles of one camera of one view, per lane
 struct RigJointTiles {
     d4 t00U, t00V, t10U, t10V, t11U, t11V;
@@ -114,10 +124,13 @@ struct RigJointTiles {
 // One camera's points of one view through the slab into the tiles. RIG = false: camera 0, columns [view 6 | shared | pad]
 // (stereo_joint_blocks_kernel's camera a). RIG = true: camera c >= 1 with vr the constants of rig_c, J0 = [view 6 | shared |
 // pad], J1 = [rig 6 | pad] (its camera b; the chain rule is written out as there).
-template <int MODEL, bool RIG>
+// ROBUST: with s = |res|^2 the point's rows and residual are scaled by sqrt(w), w = rho'(s), before they reach the slab --
+// the tiles are those of the re-weighted problem -- and t.err is the lane's own sum of rho(s) over its points, not the
+// slab's sum of squares: the caller adds up all 64 lanes. A tail lane has s = 0: w = 1, rho = 0.
+template <int MODEL, bool RIG, bool ROBUST = false>
 __device__ __forceinline__ void rig_joint_pass(const StereoCam& cm, const double* __restrict__ shared, int64_t view, int lane,
                                                const double (&vc)[kViewStride], const double (&vr)[kViewStride],
-                                               double2* slab, RigJointTiles& t) {
+                                               double2* slab, RigJointTiles& t, int lossKind = 0, double lossScale = 0.0) {
     constexpr int L = ModelTraits<MODEL>::L, C = ModelTraits<MODEL>::C;
     const int k = lane >> 4, c = lane & 15;
     const double2 zero2 = {0.0, 0.0};
@@ -169,6 +182,25 @@ __device__ __forceinline__ void rig_joint_pass(const StereoCam& cm, const double
         double2 res;
         res.x = live ? m.x - u : 0.0;
         res.y = live ? m.y - v : 0.0;
+        if constexpr (ROBUST) {
+            const double s = res.x * res.x + res.y * res.y, d2 = lossScale * lossScale;
+            double w, rho;
+            if (lossKind == kLossHuber) {                                       // launch-uniform
+                const double r = sqrt(s);
+                w = s <= d2 ? 1.0 : lossScale / r;
+                rho = s <= d2 ? s : 2.0 * lossScale * r - d2;
+            } else {
+                w = 1.0 / (1.0 + s / d2);
+                rho = d2 * log1p(s / d2);
+            }
+            const double sw = sqrt(w);
+#pragma unroll
+            for (int cc = 0; cc < 6; ++cc) { Jv[cc].x *= sw; Jv[cc].y *= sw; }
+#pragma unroll
+            for (int cc = 0; cc < (RIG ? L + 6 : L); ++cc) { J[cc].x *= sw; J[cc].y *= sw; }
+            res.x *= sw; res.y *= sw;
+            t.err += rho;
+        }
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             if (q0 + kJRows * half >= n) break;                                  // wave-uniform
@@ -202,7 +234,7 @@ __device__ __forceinline__ void rig_joint_pass(const StereoCam& cm, const double
                     t.t11V = __builtin_amdgcn_mfma_f64_16x16x4f64(j1.y, j1.y, t.t11V, 0, 0, 0);
                     t.g1 += j1.x * rr.x + j1.y * rr.y;
                 }
-                t.err += rr.x * rr.x + rr.y * rr.y;
+                if constexpr (!ROBUST) t.err += rr.x * rr.x + rr.y * rr.y;
             }
         }
     }
@@ -526,6 +558,178 @@ __global__ __launch_bounds__(64) void rig_joint_backsub_kernel(RigJointArgs a, S
             const double ds = a.dsh[s];
             bf.delta[s] = ds;
             Pn[s] = a.isFixed(s) ? Pc[s] : Pc[s] + ds;      // copied, not added to: the bits stay (-0.0 + 0.0 is +0.0)
+        }
+    }
+}
+
+// ---- robust losses -----------------------------------------------------------------------------------------
+// rig_joint_blocks_kernel on the problem re-weighted at the candidate: sum rho(|r_p|^2) instead of sum |r_p|^2, every
+// point's rows and residual times sqrt(rho') (first order: Triggs' second-order term is left out). Same slab, tiles,
+// parking, record and partial; the cameras' sums of rho stand where their errors stand, so the other four kernels of a
+// round run unchanged. Huber or Cauchy is a run-time, launch-uniform value: the kernel exists once.
+template <int NCMAX>
+__global__ __launch_bounds__(64 * kRjWaves) void rig_joint_robust_blocks_kernel(RigJointArgs a, StereoBufs bf, RigLoss loss) {
+    __shared__ __attribute__((aligned(16))) double2 smem[kRjWaves * kJSlab];
+    __shared__ double park[kRjWaves][kRjPark];
+    __shared__ double part[kRjWaves][kRjMaxTot];
+    static_assert(NCMAX == kRigMaxCams, "the partial holds eight cameras' blocks");
+    if (bf.st->done) return;
+    const RigJointDesc& d = a.d;
+    const int cand = bf.st->cur ^ 1;
+    const double* __restrict__ Pq = bf.P[cand];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int k = lane >> 4, c16 = lane & 15;
+    double2* slab = smem + wave * kJSlab;
+    double* T = park[wave];
+    double* mine = part[wave];
+    const double2 zero2 = {0.0, 0.0};
+    // chunks no pass stores (J1's pad columns) stay zero from here on; camera 0 leaves J1 as the last camera wrote it
+    // and does not read it
+    for (int j = lane; j < kJSlab; j += 64) slab[j] = zero2;
+    for (int j = lane; j < d.kTot; j += 64) mine[j] = 0.0;
+    // this lane's entry of (V | g_view): its row and column in T00, or its place in g0
+    const int va = lane < 21 ? tri_row(lane) : 0, vb = lane < 21 ? lane - va * (va + 1) / 2 : 0;
+    const int64_t stride = (int64_t)gridDim.x * kRjWaves;
+    for (int64_t view = (int64_t)blockIdx.x * kRjWaves + wave; view < bf.M; view += stride) {     // wave-uniform
+        double e[6], vc[kViewStride];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) e[j] = Pq[d.S + 6 * view + j];
+        pose_view_constants(e, vc);
+        // one view per wave: the constants are the same in every lane and live in scalar registers
+#pragma unroll
+        for (int j = 0; j < kViewStride; ++j) vc[j] = readlane_d(vc[j], 0);
+        double* __restrict__ rec = bf.rec[cand] + view * d.kStride;
+        double vacc = 0.0;                                                       // lane j < 27: entry j of (V | g_view)
+#pragma unroll 1
+        for (int c = 0; c < d.nc; ++c) {                                         // one body for every camera
+            const int L = d.L[c], off = d.off[c];
+            RigJointTiles t;
+            t.t00U = d4{0.0, 0.0, 0.0, 0.0};
+            t.t00V = t.t00U; t.t10U = t.t00U; t.t10V = t.t00U; t.t11U = t.t00U; t.t11V = t.t00U;
+            t.g0 = 0.0; t.g1 = 0.0; t.err = 0.0;
+            if (c == 0) {
+                if (d.model[0] == kRadtan) rig_joint_pass<kRadtan, false, true>(a.cam[0], Pq + off, view, lane, vc, vc, slab, t, loss.kind, loss.scale);
+                else rig_joint_pass<kFisheye, false, true>(a.cam[0], Pq + off, view, lane, vc, vc, slab, t, loss.kind, loss.scale);
+            } else {
+                double rg[6], vr[kViewStride];
+#pragma unroll
+                for (int j = 0; j < 6; ++j) rg[j] = Pq[off + L + j];
+                pose_view_constants(rg, vr);
+#pragma unroll
+                for (int j = 0; j < kViewStride; ++j) vr[j] = readlane_d(vr[j], 0);
+                if (d.model[c] == kRadtan) rig_joint_pass<kRadtan, true, true>(a.cam[c], Pq + off, view, lane, vc, vr, slab, t, loss.kind, loss.scale);
+                else rig_joint_pass<kFisheye, true, true>(a.cam[c], Pq + off, view, lane, vc, vr, slab, t, loss.kind, loss.scale);
+            }
+            // the sum of rho: every lane holds points of its own, all 64 in one fixed order
+            t.err += __shfl_xor(t.err, 1, 64);  t.err += __shfl_xor(t.err, 2, 64);
+            t.err += __shfl_xor(t.err, 4, 64);  t.err += __shfl_xor(t.err, 8, 64);
+            // the four points of a group sit in the four 16-lane rows of the wave
+            t.g0 += __shfl_xor(t.g0, 16, 64);   t.g0 += __shfl_xor(t.g0, 32, 64);
+            t.g1 += __shfl_xor(t.g1, 16, 64);   t.g1 += __shfl_xor(t.g1, 32, 64);
+            t.err += __shfl_xor(t.err, 16, 64); t.err += __shfl_xor(t.err, 32, 64);
+            __builtin_amdgcn_wave_barrier();                                     // the last camera's readers are through
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                const int o = (k + 4 * reg) * 16 + c16;
+                T[kRjT00 + o] = t.t00U[reg] + t.t00V[reg];
+                T[kRjT10 + o] = t.t10U[reg] + t.t10V[reg];
+                T[kRjT11 + o] = t.t11U[reg] + t.t11V[reg];
+            }
+            if (k == 0) { T[kRjG0 + c16] = t.g0; T[kRjG1 + c16] = t.g1; }
+            if (lane == 0) T[kRjE] = t.err;
+            __builtin_amdgcn_wave_barrier();
+            // V and g_view over the cameras in index order
+            if (lane < 21) vacc += T[kRjT00 + va * 16 + vb];
+            else if (lane < 27) vacc += T[kRjG0 + lane - 21];
+            // the camera's band of E (a camera without points in the view: exact zeros)
+            const int W = d.width(c);
+            for (int j = lane; j < 6 * W; j += 64) {
+                const int s = j / 6, v = j - 6 * s;
+                rec[kRjE0 + (off + s) * 6 + v] = s < L ? T[kRjT00 + (6 + s) * 16 + v] : T[kRjT10 + (s - L) * 16 + v];
+            }
+            // its B block, g and error into the wave's resident partial: the wave's views in index order
+            const int nb = W * (W + 1) / 2;
+            for (int eI = lane; eI < nb; eI += 64) {
+                const int i = tri_row(eI), j = eI - i * (i + 1) / 2;
+                mine[d.bo[c] + eI] += i < L ? T[kRjT00 + (6 + i) * 16 + 6 + j]
+                                            : j < L ? T[kRjT10 + (i - L) * 16 + 6 + j] : T[kRjT11 + (i - L) * 16 + (j - L)];
+            }
+            if (lane < W) mine[d.kG + off + lane] += lane < L ? T[kRjG0 + 6 + lane] : T[kRjG1 + lane - L];
+            if (lane == 0) mine[d.kErr + c] += T[kRjE];
+        }
+        if (lane < 21) rec[lane] = vacc;
+        else if (lane < 27) rec[d.kGv + lane - 21] = vacc;
+    }
+    __syncthreads();
+    // the workgroup's waves in index order
+    for (int eI = threadIdx.x; eI < d.kTot; eI += 64 * kRjWaves) {
+        double s = part[0][eI];
+#pragma unroll
+        for (int w = 1; w < kRjWaves; ++w) s += part[w][eI];
+        bf.partA[cand][(int64_t)blockIdx.x * d.kTot + eI] = s;
+    }
+}
+
+// one camera's points of one view: sensor - projection into res (the camera's own rows)
+template <int MODEL, bool RIG>
+__device__ __forceinline__ void rig_residuals_pass(const StereoCam& cm, const double* __restrict__ shared, int64_t view, int lane,
+                                                   const double (&vc)[kViewStride], const double (&vr)[kViewStride],
+                                                   double2* __restrict__ res) {
+    Shared<MODEL, double> sp;
+    sp.load(shared);
+    const int64_t p0 = cm.offs[view];
+    const int n = (int)(cm.offs[view + 1] - p0);
+    for (int q = lane; q < n; q += 64) {
+        const int64_t p = p0 + q;
+        const double2 m = cm.uv[p];
+        const double* X = cm.xyz + 3 * p;
+        double u, v;
+        if constexpr (RIG) {
+            const double qx = vc[0] * X[0] + vc[1] * X[1] + vc[2] * X[2];       // R_i X
+            const double qy = vc[3] * X[0] + vc[4] * X[1] + vc[5] * X[2];
+            const double qz = vc[6] * X[0] + vc[7] * X[1] + vc[8] * X[2];
+            project_point<MODEL, double>(sp, vr, qx + vc[9], qy + vc[10], qz + vc[11], u, v);
+        } else {
+            project_point<MODEL, double>(sp, vc, X[0], X[1], X[2], u, v);
+        }
+        res[p] = double2{m.x - u, m.y - v};
+    }
+}
+
+// Every point's residual at Pq, one wave per view, the cameras in index order: out holds camera 0's n_0 rows, then camera
+// 1's, .. (2 doubles a point, nothing else). Four waves per workgroup; the grid's waves loop over the views.
+constexpr int kRjResidualWaves = 4, kRjResidualGrid = 1024;
+template <int NCMAX>
+__global__ __launch_bounds__(64 * kRjResidualWaves) void rig_residuals_kernel(RigJointArgs a, const double* __restrict__ Pq,
+                                                                               int64_t M, double2* __restrict__ out) {
+    const RigJointDesc& d = a.d;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t stride = (int64_t)gridDim.x * kRjResidualWaves;
+    for (int64_t view = (int64_t)blockIdx.x * kRjResidualWaves + wave; view < M; view += stride) {     // wave-uniform
+        double e[6], vc[kViewStride];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) e[j] = Pq[d.S + 6 * view + j];
+        pose_view_constants(e, vc);
+#pragma unroll
+        for (int j = 0; j < kViewStride; ++j) vc[j] = readlane_d(vc[j], 0);
+        double2* res = out;
+#pragma unroll 1
+        for (int c = 0; c < d.nc; ++c) {
+            const int L = d.L[c], off = d.off[c];
+            if (c == 0) {
+                if (d.model[0] == kRadtan) rig_residuals_pass<kRadtan, false>(a.cam[0], Pq + off, view, lane, vc, vc, res);
+                else rig_residuals_pass<kFisheye, false>(a.cam[0], Pq + off, view, lane, vc, vc, res);
+            } else {
+                double rg[6], vr[kViewStride];
+#pragma unroll
+                for (int j = 0; j < 6; ++j) rg[j] = Pq[off + L + j];
+                pose_view_constants(rg, vr);
+#pragma unroll
+                for (int j = 0; j < kViewStride; ++j) vr[j] = readlane_d(vr[j], 0);
+                if (d.model[c] == kRadtan) rig_residuals_pass<kRadtan, true>(a.cam[c], Pq + off, view, lane, vc, vr, res);
+                else rig_residuals_pass<kFisheye, true>(a.cam[c], Pq + off, view, lane, vc, vr, res);
+            }
+            res += a.cam[c].offs[M];                                             // the camera's points over all views
         }
     }
 }

@@ -2,7 +2,8 @@
 // joint stereo (stereo_joint.hpp), the rig of N known cameras (rig.hpp) and the joint rig (rig_joint.hpp). Included once
 // by calib_lm.hip, after the kernel headers and its own helpers (fail, HIP_TRY, LAUNCHED, DevBuf, dispatch_model,
 // check_views, use_device). What a solver is on the host is one descriptor (solver_desc); one checker, one begin and
-// three drivers (solver_normal_eq, solver_step_delta, solver_refine) serve all four.
+// three drivers (solver_normal_eq, solver_step_delta, solver_refine) serve all four. A robust loss (the joint rig's) is a
+// member of the run: begin() then takes the solver's evaluate_robust; the drivers are the same.
 #pragma once
 #include "block_map.hpp"
 
@@ -59,6 +60,8 @@ struct StereoSolver {
     int grid_a = 0, grid_c = 0;             // > 0: the blocks / Schur kernel's grid loops over its views, at most so many partials
     bool known_cameras = false;             // the cameras' shared vectors are required and uploaded (else they travel in P)
     bool rig_joint = false;                 // the joint rig's extras: rj, the step's shared part, both mask words as arguments
+    int (*evaluate_robust)(const StereoRun&) = nullptr;     // evaluate under the run's loss (the joint rig alone has one)
+    int (*residuals)(const StereoRun&, const double*, double*) = nullptr;   // every point's residual at a device P
     RigJointDesc rj{};
     BlockMap map;
 };
@@ -136,6 +139,7 @@ struct StereoRun {
     DevBuf<double> P[2], rec[2], partA[2], tot, partC, delta, trace;
     DevBuf<double> dshq;                    // the joint rig solver's shared step (StereoState::dsh holds kJMaxS entries)
     SolverMask fixed;                       // over all S shared unknowns
+    RigLoss loss{CALIB_LOSS_NONE, 0.0};     // a robust loss: begin() then takes the solver's evaluate_robust
     DevBuf<StereoState> st;
     DoneWord done;
     int64_t M = 0;
@@ -167,6 +171,10 @@ struct StereoRun {
     int begin(StereoSolver solver, int64_t num_views, const double* P0, const SolverMask& mask, int max_iters, double lam,
               double lam_min, double lam_max, double err_min, bool want_trace, bool want_notify) {
         sv = std::move(solver);
+        if (loss.kind != CALIB_LOSS_NONE) {
+            if (!sv.evaluate_robust) return fail(CALIB_E_INVALID, "this solver has no robust loss");
+            sv.evaluate = sv.evaluate_robust;
+        }
         fixed = mask;
         M = num_views;
         nwgA = (int)((M + sv.views_a - 1) / sv.views_a);
@@ -215,11 +223,24 @@ struct StereoRun {
     }
 };
 
+// A loss as the robust entry points take it: NULL or CALIB_LOSS_NONE is no loss (the plain entry point serves it, whatever
+// the scale says); otherwise the kind is Huber or Cauchy and the scale finite and > 0.
+int check_loss(const calib_loss_t* loss) {
+    if (loss->kind != CALIB_LOSS_HUBER && loss->kind != CALIB_LOSS_CAUCHY) return fail(CALIB_E_INVALID, "unknown loss kind");
+    if (!(std::isfinite(loss->scale) && loss->scale > 0.0)) return fail(CALIB_E_INVALID, "the scale of a loss must be finite and > 0");
+    return CALIB_OK;
+}
+bool loss_is_plain(const calib_loss_t* loss) { return !loss || loss->kind == CALIB_LOSS_NONE; }
+
 // One begin: checks, device, the cameras and the run's buffers with P as the start point
 int solver_begin(StereoRun& run, SolverKind kind, const SolverProblem& pb, const double* P, const SolverMask& mask, int max_iters,
-                 double lam, double lam_min, double lam_max, double err_min, bool want_trace, bool want_notify, int device_id) {
+                 double lam, double lam_min, double lam_max, double err_min, bool want_trace, bool want_notify, int device_id,
+                 const calib_loss_t* loss = nullptr) {
     StereoSolver sv{};
-    int rc = check_problem(kind, pb, P, mask, sv);
+    int rc = loss_is_plain(loss) ? CALIB_OK : check_loss(loss);
+    if (rc) return rc;
+    if (!loss_is_plain(loss)) run.loss = RigLoss{loss->kind, loss->scale};
+    rc = check_problem(kind, pb, P, mask, sv);
     if (rc) return rc;
     rc = use_device(device_id);
     if (rc) return rc;
@@ -293,10 +314,10 @@ int run_refine(StereoRun& run, double* P_inout, int max_iters, double* out_sse, 
 
 // ---- the three drivers behind the twelve entry points ------------------------------------------------------------------
 int solver_normal_eq(SolverKind kind, const SolverProblem& pb, const double* P, double* out_B, double* out_E, double* out_V,
-                     double* out_g, double* out_sse_cam, int device_id) {
+                     double* out_g, double* out_sse_cam, int device_id, const calib_loss_t* loss = nullptr) {
     StereoRun run;
     std::vector<double> rec, tot;
-    int rc = solver_begin(run, kind, pb, P, SolverMask(), 1, 0.0, 0.0, 0.0, 0.0, false, false, device_id);
+    int rc = solver_begin(run, kind, pb, P, SolverMask(), 1, 0.0, 0.0, 0.0, 0.0, false, false, device_id, loss);
     if (rc) return rc;
     rc = run_blocks(run, rec, tot);
     if (rc) return rc;
@@ -305,20 +326,48 @@ int solver_normal_eq(SolverKind kind, const SolverProblem& pb, const double* P, 
 }
 
 int solver_step_delta(SolverKind kind, const SolverProblem& pb, const double* P, const SolverMask& mask, double lambda,
-                      double* out_delta, int device_id) {
+                      double* out_delta, int device_id, const calib_loss_t* loss = nullptr) {
     StereoRun run;
-    const int rc = solver_begin(run, kind, pb, P, mask, 1, lambda, 0.0, 0.0, 0.0, false, false, device_id);
+    const int rc = solver_begin(run, kind, pb, P, mask, 1, lambda, 0.0, 0.0, 0.0, false, false, device_id, loss);
     return rc ? rc : run_step_delta(run, out_delta);
 }
 
 int solver_refine(SolverKind kind, const SolverProblem& pb, double* P_inout, const SolverMask& mask, int max_iters,
                   double lam_init, double lam_min, double lam_max, double err_min, double* out_sse, double* out_sse_cam,
-                  int* out_iters, double* out_trace, int device_id) {
+                  int* out_iters, double* out_trace, int device_id, const calib_loss_t* loss = nullptr) {
     if (max_iters <= 0) return fail(CALIB_E_INVALID, "max_iters must be >= 1");
     StereoRun run;
     const int rc = solver_begin(run, kind, pb, P_inout, mask, max_iters, lam_init, lam_min, lam_max, err_min,
-                                out_trace != nullptr, true, device_id);
+                                out_trace != nullptr, true, device_id, loss);
     return rc ? rc : run_refine(run, P_inout, max_iters, out_sse, out_sse_cam, out_iters, out_trace);
+}
+
+// every point's residual at P, the cameras one after the other: no loop, no buffers but the cameras, P and the result
+int solver_residuals(SolverKind kind, const SolverProblem& pb, const double* P, double* out_res, int device_id) {
+    StereoRun run;
+    int rc = check_problem(kind, pb, P, SolverMask(), run.sv);
+    if (rc) return rc;
+    if (!out_res) return fail(CALIB_E_INVALID, "null argument");
+    if (!run.sv.residuals) return fail(CALIB_E_INVALID, "this solver has no residual kernel");
+    rc = use_device(device_id);
+    if (rc) return rc;
+    run.ncam = pb.ncam;
+    run.M = pb.M;
+    size_t n = 0;
+    for (int c = 0; c < pb.ncam; ++c) {
+        rc = run.upload_cam(c, pb.cams[c], pb.M, run.sv.known_cameras);
+        if (rc) return rc;
+        n += (size_t)pb.cams[c].offs[pb.M];
+    }
+    if (!n) return CALIB_OK;
+    DevBuf<double> res;
+    HIP_TRY(run.P[0].alloc(run.params()));
+    HIP_TRY(res.alloc(2 * n));
+    HIP_TRY(hipMemcpy(run.P[0].p, P, run.params() * 8, hipMemcpyHostToDevice));
+    rc = run.sv.residuals(run, run.P[0].p, res.p);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(out_res, res.p, 2 * n * 8, hipMemcpyDeviceToHost));
+    return CALIB_OK;
 }
 
 }  // namespace

@@ -788,7 +788,8 @@ def rigJointLayout(modelIds):
 # kind: (S from the model ids; the C entry points of the normal equations, the step and the loop; how the fixed mask
 # travels: None = the cameras are known and their shared vectors are read, no mask; "int"; "words" = two uint64, NULL for 0).
 # The "stereo" kinds take two cameras in a calib_stereo_problem_t, tag them a and b and return their errors as sseA, sseB;
-# the "rig" kinds take 2 to 8 in a calib_rig_problem_t, number them and return sseCam.
+# the "rig" kinds take 2 to 8 in a calib_rig_problem_t, number them and return sseCam. "rigRobust" is "rigJoint" under a
+# loss (parseLoss): its entry points take a calib_loss_t after the mask, and its errors are sums of rho.
 _SOLVERS = {
     "stereo": (lambda ids: 6, "calib_stereo_normal_eq", "calib_stereo_step_delta", "calib_refine_stereo", None),
     "stereoJoint": (lambda ids: NUM_SHARED[ids[0]] + NUM_SHARED[ids[1]] + 6, "calib_stereo_joint_normal_eq",
@@ -796,7 +797,61 @@ _SOLVERS = {
     "rig": (lambda ids: 6 * (len(ids) - 1), "calib_rig_normal_eq", "calib_rig_step_delta", "calib_refine_rig", None),
     "rigJoint": (lambda ids: rigJointLayout(ids)[0], "calib_rig_joint_normal_eq", "calib_rig_joint_step_delta",
                  "calib_refine_rig_joint", "words"),
+    "rigRobust": (lambda ids: rigJointLayout(ids)[0], "calib_rig_robust_normal_eq", "calib_rig_robust_step_delta",
+                  "calib_refine_rig_robust", "words"),
 }
+LOSS_KINDS = {"huber": nat.LOSS_HUBER, "cauchy": nat.LOSS_CAUCHY}
+
+
+def parseLoss(loss):
+    """None, "huber", "cauchy" or (name, scale) -> None or (name, scale in pixels, default 1.0); ValueError otherwise"""
+    if loss is None:
+        return None
+    if isinstance(loss, str):
+        name, scale = loss, 1.0
+    elif isinstance(loss, (tuple, list)) and len(loss) == 2:
+        name, scale = loss
+    else:
+        name, scale = None, None
+    if not isinstance(name, str) or name not in LOSS_KINDS:
+        raise ValueError(f"loss: expected None, 'huber', 'cauchy' or (name, scale), got {loss!r}")
+    if isinstance(scale, bool) or not isinstance(scale, (int, float, np.integer, np.floating)):
+        raise ValueError(f"loss: the scale must be a number of pixels, got {scale!r}")
+    scale = float(scale)
+    if not (np.isfinite(scale) and scale > 0.0):
+        raise ValueError(f"loss: the scale must be finite and > 0, got {scale!r}")
+    return name, scale
+
+
+def _lossArgument(kind, loss):
+    """what the C call of `kind` takes between the mask and the next argument: nothing, or a calib_loss_t (NULL = none)"""
+    if kind != "rigRobust":
+        return []
+    loss = parseLoss(loss)
+    return [None if loss is None else ctypes.byref(nat.Loss(LOSS_KINDS[loss[0]], loss[1]))]
+
+
+def lossRho(loss, s):
+    """rho(s) of a parsed loss (None: s) at s = |r|^2, the formulas of include/calib_lm.h on the host"""
+    s = np.asarray(s, dtype=np.float64)
+    if loss is None:
+        return s.copy()
+    name, d = parseLoss(loss)
+    if name == "huber":
+        return np.where(s <= d * d, s, 2.0 * d * np.sqrt(s) - d * d)
+    return d * d * np.log1p(s / (d * d))
+
+
+def lossWeight(loss, s):
+    """w = rho'(s)"""
+    s = np.asarray(s, dtype=np.float64)
+    if loss is None:
+        return np.ones_like(s)
+    name, d = parseLoss(loss)
+    if name == "huber":
+        with np.errstate(divide="ignore"):
+            return np.where(s <= d * d, 1.0, d / np.sqrt(s))
+    return 1.0 / (1.0 + s / (d * d))
 
 
 def _solverProblem(kind, cameras, P=None, fixedMask=0):
@@ -804,7 +859,7 @@ def _solverProblem(kind, cameras, P=None, fixedMask=0):
     unknowns of the kind, pose_0, ..) -> (the C struct, the arrays it points into: keep them alive for the call, M, S,
     P (S + 6 M,), the mask as the C call takes it). The joint kinds do not read the cameras' own shared vectors: the
     cameras travel in P. Without P only the cameras are packed and checked."""
-    numShared, _, _, _, maskAs = _SOLVERS[kind]
+    numShared, maskAs = _SOLVERS[kind][0], _SOLVERS[kind][4]
     pair, joint = kind.startswith("stereo"), maskAs is not None
     cameras = tuple(cameras)
     N = len(cameras)
@@ -866,35 +921,39 @@ def _cameraErrors(kind, cam):
     return (float(cam[0]), float(cam[1])) if kind.startswith("stereo") else cam
 
 
-def _solverNormalEquations(kind, cameras, P, device):
+def _solverNormalEquations(kind, cameras, P, device, loss=None):
     cameras = tuple(cameras)
+    lossArg = _lossArgument(kind, loss)
     prob, keep, M, S, P, _ = _solverProblem(kind, cameras, P)
     B, E, V, g = np.empty((S, S)), np.empty((M, S, 6)), np.empty((M, 6, 6)), np.empty(S + 6 * M)
     cam = np.empty(len(cameras))
-    nat.check(getattr(nat.loadLibrary(), _SOLVERS[kind][1])(ctypes.byref(prob), nat.dptr(P), nat.dptr(B), nat.dptr(E),
+    nat.check(getattr(nat.loadLibrary(), _SOLVERS[kind][1])(ctypes.byref(prob), nat.dptr(P), *lossArg, nat.dptr(B), nat.dptr(E),
                                                             nat.dptr(V), nat.dptr(g), nat.dptr(cam), int(device)))
-    errors = {"sseA": float(cam[0]), "sseB": float(cam[1])} if kind.startswith("stereo") else {"sseCam": cam}
+    errors = ({"sseA": float(cam[0]), "sseB": float(cam[1])} if kind.startswith("stereo")
+              else {"costCam" if kind == "rigRobust" else "sseCam": cam})
     return {"B": B, "E": E, "V": V, "g": g, **errors}
 
 
-def _solverStepDelta(kind, cameras, P, lam, fixedMask, device):
+def _solverStepDelta(kind, cameras, P, lam, fixedMask, device, loss=None):
+    lossArg = _lossArgument(kind, loss)
     prob, keep, M, S, P, mask = _solverProblem(kind, cameras, P, fixedMask)
     delta = np.empty(S + 6 * M)
     nat.check(getattr(nat.loadLibrary(), _SOLVERS[kind][2])(
-        ctypes.byref(prob), nat.dptr(P), *([] if _SOLVERS[kind][4] is None else [mask]), float(lam), nat.dptr(delta),
-        int(device)))
+        ctypes.byref(prob), nat.dptr(P), *([] if _SOLVERS[kind][4] is None else [mask]), *lossArg, float(lam),
+        nat.dptr(delta), int(device)))
     return delta
 
 
-def _solverRefine(kind, cameras, P0, maxIters, fixedMask, lamInit, lamMin, lamMax, errMin, device):
+def _solverRefine(kind, cameras, P0, maxIters, fixedMask, lamInit, lamMin, lamMax, errMin, device, loss=None):
     cameras = tuple(cameras)
+    lossArg = _lossArgument(kind, loss)
     prob, keep, M, S, P, mask = _solverProblem(kind, cameras, P0, fixedMask)
     P = P.copy()
     maxIters = int(maxIters)
     sse, iters, cam = ctypes.c_double(0.0), ctypes.c_int(0), np.empty(len(cameras))
     trace = np.zeros((max(maxIters, 1), nat.TRACE_HEADER + S))
     nat.check(getattr(nat.loadLibrary(), _SOLVERS[kind][3])(
-        ctypes.byref(prob), nat.dptr(P), *([] if _SOLVERS[kind][4] is None else [mask]), maxIters, float(lamInit),
+        ctypes.byref(prob), nat.dptr(P), *([] if _SOLVERS[kind][4] is None else [mask]), *lossArg, maxIters, float(lamInit),
         float(lamMin), float(lamMax), float(errMin), ctypes.byref(sse), nat.dptr(cam), ctypes.byref(iters), nat.dptr(trace),
         int(device)))
     return sse.value, P, iters.value, trace[:iters.value], _cameraErrors(kind, cam)
@@ -972,6 +1031,34 @@ def refineRigJoint(cameras, Pq0, maxIters, fixedMask=0, lamInit=LAMBDA_INITIAL, 
     """The LM loop on Pq -> (sse [pre-update, as the reference returns], Pq, iters, trace (iters, 5 + S), sseCam (N,) at
     the returned Pq)."""
     return _solverRefine("rigJoint", cameras, Pq0, maxIters, fixedMask, lamInit, lamMin, lamMax, errMin, device)
+
+
+def rigRobustNormalEquations(cameras, Pq, loss, device=0):
+    """rigJointNormalEquations of the problem re-weighted by `loss` (parseLoss) at Pq: every point's rows and residual
+    times sqrt(rho'(|r|^2)) -> dict B, E, V, g as there, costCam (N,) = sum rho per camera. loss=None is the plain call."""
+    return _solverNormalEquations("rigRobust", cameras, Pq, device, loss)
+
+
+def rigRobustStepDelta(cameras, Pq, lam, loss, fixedMask=0, device=0):
+    """delta (S + 6 M,) = the LM step of the re-weighted joint rig problem at Pq, the unknowns of fixedMask held."""
+    return _solverStepDelta("rigRobust", cameras, Pq, lam, fixedMask, device, loss)
+
+
+def refineRigRobust(cameras, Pq0, maxIters, loss, fixedMask=0, lamInit=LAMBDA_INITIAL, lamMin=LAMBDA_MIN, lamMax=LAMBDA_MAX,
+                    errMin=PT_ERROR_MIN, device=0):
+    """refineRigJoint on sum rho -> (cost [sum rho before the last update], Pq, iters, trace (iters, 5 + S) with sum rho
+    in columns 1 and 2, costCam (N,) at the returned Pq)."""
+    return _solverRefine("rigRobust", cameras, Pq0, maxIters, fixedMask, lamInit, lamMin, lamMax, errMin, device, loss)
+
+
+def rigResiduals(cameras, Pq, device=0):
+    """sensor - projection of every point of the joint rig problem at Pq -> list of (n_c, 2), one array per camera"""
+    cameras = tuple(cameras)
+    prob, keep, M, S, P, _ = _solverProblem("rigJoint", cameras, Pq)
+    counts = [int(np.asarray(cam[2])[-1]) for cam in cameras]
+    res = np.empty((sum(counts), 2))
+    nat.check(nat.loadLibrary().calib_rig_residuals(ctypes.byref(prob), nat.dptr(P), nat.dptr(res), int(device)))
+    return [a.copy() for a in np.split(res, np.cumsum(counts)[:-1])]
 
 
 # ---- using a calibrated rig (calib_rectify_*, calib_triangulate, csrc/rectify.hpp): arguments are checked first --------

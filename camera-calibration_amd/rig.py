@@ -65,12 +65,20 @@ class RigCalibration:
     From a joint run (rigCalibrate(refineCameras=True)): Pq = (shared_0 | shared_1, rig_1 | .. | pose_0, ..) the joint
     parameter vector, fixedMask (a Python int) over its S shared unknowns, trace (iters, 5 + S) the joint loop's, rigOnly
     the RigCalibration of the rig-only refinement it continued from; cameras(), rectify, triangulate and triangulateAll
-    use the refined cameras."""
+    use the refined cameras.
+    From a robust run (rigCalibrate(loss=...)): loss the parsed (name, scale), cost / costCam the sums of rho(|r|^2) at
+    the result and sseBeforeLastUpdate the robust loop's own return (a sum of rho), trace the robust loop's; sseCam, sse
+    and rms stay the plain sums of |r|^2 at the result, comparable with an L2 run; Pq, fixedMask and rigOnly as from a
+    joint run (with refineCameras=False the mask holds every camera bit). Without a loss: loss None, cost = sse."""
 
-    def __init__(self, sseBeforeLastUpdate, Pr, iters, trace, sseCam, problem, device, Pq=None, fixedMask=0, rigOnly=None):
+    def __init__(self, sseBeforeLastUpdate, Pr, iters, trace, sseCam, problem, device, Pq=None, fixedMask=0, rigOnly=None,
+                 loss=None, costCam=None, camerasHeld=False):
         N = len(problem)
         S = 6 * (N - 1)
         self.Pq, self.fixedMask, self.rigOnly = Pq, fixedMask, rigOnly
+        self.loss, self._camerasHeld = loss, camerasHeld
+        self.costCam = np.asarray(sseCam if costCam is None else costCam, dtype=np.float64)
+        self.cost = float(self.costCam.sum())
         self.Pr, self.iters, self.trace, self.sseBeforeLastUpdate = Pr, iters, trace, sseBeforeLastUpdate
         self.sseCam = np.asarray(sseCam, dtype=np.float64)
         self.sse = float(self.sseCam.sum())
@@ -93,7 +101,17 @@ class RigCalibration:
         """Covariance (S,S) of the rig parameters (parameterNames) at the result: sigma^2 S_undamped^-1 with
         sigma^2 = sse / (2 n - S - 6 M), the units of CalibrationUncertainty. From a joint run: of the S shared unknowns
         of the joint problem (jointParameterNames), sigma^2 S_free^-1 with dof = 2 n - (S - |F|) - 6 M; rows and columns
-        of fixed parameters are exact zeros."""
+        of fixed parameters are exact zeros. From a robust run: of the WEIGHTED blocks (every point's rows times
+        sqrt(rho'), first order), sigma^2 = sum_p w_p |r_p|^2 / dof with the plain run's dof; a run that held the cameras
+        (refineCameras=False) returns the rig rows and columns only, in parameterNames() order."""
+        if self.loss is not None:
+            ne = engine.rigRobustNormalEquations(self._problem, self.Pq, self.loss, self._device)
+            wss = sum(float(np.sum(w * np.sum(r * r, axis=1))) for w, r in zip(self.weights(), self.residuals()))
+            C = jointCovarianceFromBlocks(ne["B"], ne["E"], ne["V"], wss, int(self.numPoints.sum()), self.fixedMask)
+            if not self._camerasHeld:
+                return C
+            rigs = self._rigColumns()
+            return C[np.ix_(rigs, rigs)].copy()
         if self.Pq is not None:
             ne = engine.rigJointNormalEquations(self._problem, self.Pq, self._device)
             return jointCovarianceFromBlocks(ne["B"], ne["E"], ne["V"], float(ne["sseCam"].sum()),
@@ -105,11 +123,27 @@ class RigCalibration:
         """the 6 x 6 block of covariance() of camera c >= 1 (rho_x, rho_y, rho_z in DEGREES, then t)"""
         if not 1 <= c < self.numCameras:
             raise ValueError(f"camera {c!r} has no rig: expected 1 <= c < {self.numCameras}")
-        if self.Pq is not None:
+        if self.Pq is not None and not self._camerasHeld:
             _, off, L = engine.rigJointLayout([cam[0] for cam in self._problem])
             r = slice(off[c] + L[c], off[c] + L[c] + 6)
             return self.covariance()[r, r].copy()
         return self.covariance()[6 * (c - 1):6 * c, 6 * (c - 1):6 * c].copy()
+
+    def _rigColumns(self):
+        """the rig unknowns' places among Pq's shared ones, in parameterNames() order"""
+        _, off, L = engine.rigJointLayout([cam[0] for cam in self._problem])
+        return np.concatenate([np.arange(off[c] + L[c], off[c] + L[c] + 6) for c in range(1, self.numCameras)])
+
+    def residuals(self):
+        """list of (n_c, 2): sensor - projection of every point at the result, on the device (a robust run's)"""
+        if self.Pq is None:
+            raise ValueError("residuals() belongs to a result with a joint parameter vector: pass loss= or refineCameras=True")
+        return engine.rigResiduals(self._problem, self.Pq, self._device)
+
+    def weights(self):
+        """list of (n_c,): rho'(|r|^2) of residuals() under the run's loss, 1 without one -- small where the loss took a
+        point for an outlier"""
+        return [engine.lossWeight(self.loss, np.sum(r * r, axis=1)) for r in self.residuals()]
 
     def parameterNames(self):
         """names of the S rig unknowns: rig1.rx .. rig{N-1}.tz"""
@@ -198,14 +232,19 @@ def unpackJoint(modelIds, Pq):
     return shared, np.concatenate(rigs + [Pq[S:]])
 
 
-def rigCalibrate(detections, cameras, maxIters=50, device=0, refineCameras=False, fixed=None, fixedRigs=()):
+def rigCalibrate(detections, cameras, maxIters=50, device=0, refineCameras=False, fixed=None, fixedRigs=(), loss=None):
     """The rigs between N KNOWN cameras, 2 <= N <= 8. cameras[c] = (distortionType, A (3,3), k); detections[c]: a list of
     length M, entry i a (sensor (n,2), model (n,3)) pair of view i in camera c, or None / empty where the camera did not
     see the board (the cameras may see different corners). -> RigCalibration.
     refineCameras=True continues from that result with the cameras free: every camera's intrinsics and distortion, the
     rigs and the poses refined together. fixed: one Calibrator(fixed=...)-style spec per camera (values of a {name: value}
-    mapping are written into the joint start point); fixedRigs: the cameras c >= 1 whose rig is held there."""
+    mapping are written into the joint start point); fixedRigs: the cameras c >= 1 whose rig is held there.
+    loss: None, "huber", "cauchy" or (name, scale in pixels, default 1.0) -- a robust loss per point. The plain rig-only
+    refinement runs as without one (kept as result.rigOnly); ONE robust loop (calib_refine_rig_robust) continues from its
+    result, with every camera held unless refineCameras, then with fixed / fixedRigs. Two cameras go through here too:
+    stereoCalibrate has no loss."""
     fixedSpecs = fixed
+    loss = engine.parseLoss(loss)
     if not refineCameras and (fixedSpecs is not None or len(tuple(fixedRigs))):
         raise ValueError("fixed / fixedRigs apply to the joint refinement: pass refineCameras=True")
     if len(detections) != len(cameras) or not 2 <= len(cameras) <= 8:
@@ -221,23 +260,34 @@ def rigCalibrate(detections, cameras, maxIters=50, device=0, refineCameras=False
     problem = tuple((cam[1], cam[4]) + engine.packDetections(v) for cam, v in zip(cams, views))
     sse, Pr, iters, trace, sseCam = engine.refineRig(problem, Pr0, maxIters, device=device)
     result = RigCalibration(sse, Pr, iters, trace, sseCam, problem, device)
-    if not refineCameras:
+    if not refineCameras and loss is None:
         return result
     from . import fixed as fixedModule
     modelIds = [cam[1] for cam in cams]
-    mask, values = jointFixed(modelIds, fixedSpecs, tuple(fixedRigs))
+    if refineCameras:
+        mask, values = jointFixed(modelIds, fixedSpecs, tuple(fixedRigs))
+    else:                                                          # the robust rig-only problem: every camera bit
+        _, off, L = engine.rigJointLayout(modelIds)
+        mask, values = sum(((1 << L[c]) - 1) << off[c] for c in range(len(cams))), {}
     Pq0 = fixedModule.applyFixedValues(packJoint([cam[4] for cam in cams], Pr), values)
+    if loss is not None:
+        cost, Pq, iters, trace, costCam = engine.refineRigRobust(problem, Pq0, maxIters, loss, mask, device=device)
+        shared, PrJ = unpackJoint(modelIds, Pq)
+        refined = tuple((p[0], sh) + p[2:] for p, sh in zip(problem, shared))
+        sseCam = [float(np.sum(r * r)) for r in engine.rigResiduals(refined, Pq, device)]
+        return RigCalibration(cost, PrJ, iters, trace, sseCam, refined, device, Pq=Pq, fixedMask=mask, rigOnly=result,
+                              loss=loss, costCam=costCam, camerasHeld=not refineCameras)
     sse, Pq, iters, trace, sseCam = engine.refineRigJoint(problem, Pq0, maxIters, mask, device=device)
     shared, PrJ = unpackJoint(modelIds, Pq)
     refined = tuple((p[0], sh) + p[2:] for p, sh in zip(problem, shared))
     return RigCalibration(sse, PrJ, iters, trace, sseCam, refined, device, Pq=Pq, fixedMask=mask, rigOnly=result)
 
 
-def calibrateRig(detections, types, maxIters, device=0, joint=False):
+def calibrateRig(detections, types, maxIters, device=0, joint=False, loss=None):
     """Every camera from scratch, then the rigs: calibrateCamera on each camera's own non-empty views, then rigCalibrate
     with the results held fixed. -> (results, rig), results[c] = (sse, A, W, k) as calibrateCamera returns it (W over that
     camera's non-empty views, in order). joint=True passes refineCameras=True: rig.cameras() then holds the jointly refined
-    (A, k); results stay the mono ones."""
+    (A, k); results stay the mono ones. loss: rigCalibrate's -- the mono calibrations stay plain."""
     if len(detections) != len(types):
         raise ValueError(f"expected a distortion type per camera, got {len(types)} for {len(detections)} cameras")
     results = []
@@ -245,5 +295,5 @@ def calibrateRig(detections, types, maxIters, device=0, joint=False):
         own = [v for v in _views(dets, c) if v[0].shape[0] > 0]
         results.append(calibrateCamera(own, distortionType, maxIters, device=device))
     rig = rigCalibrate(detections, [(t, A, k) for t, (_, A, _, k) in zip(types, results)], maxIters, device,
-                       refineCameras=bool(joint))
+                       refineCameras=bool(joint), loss=loss)
     return results, rig

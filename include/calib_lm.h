@@ -500,6 +500,42 @@ int calib_refine_rig_joint(const calib_rig_problem_t* problem, double* Pq_inout,
                            int max_iters, double lam_init, double lam_min, double lam_max, double err_min, double* out_sse,
                            double* out_sse_cam, int* out_iters, double* out_trace, int device_id);
 
+/* ---- robust losses on the joint rig problem ---------------------------------------------------------------------------
+ * The joint rig entry points above with sum_p rho(s_p) in the place of sum_p s_p, s_p = rx^2 + ry^2 the squared length
+ * of point p's 2-vector residual (a loss is per point, not per coordinate), over all points of all cameras:
+ *   CALIB_LOSS_NONE    rho(s) = s
+ *   CALIB_LOSS_HUBER   rho(s) = s for s <= d^2, 2 d sqrt(s) - d^2 above;   w = rho'(s) = 1, d / sqrt(s) above
+ *   CALIB_LOSS_CAUCHY  rho(s) = d^2 log1p(s / d^2);                        w = 1 / (1 + s / d^2)
+ * d = scale, in pixels, finite and > 0. The step is the LM step of the re-weighted problem: a point's two Jacobian rows
+ * and its residual are multiplied by sqrt(w) at the current point (first order, IRLS; the second-order term of Triggs'
+ * correction is left out). Accept rule, lambda schedule, stop rule and trace are calib_refine_rig_joint's, on sum rho.
+ * Problem, Pq, fixed_mask, outputs and errors are those of the joint rig entry points; with every camera bit set the
+ * problem is the robust rig-only one. loss == NULL or kind CALIB_LOSS_NONE IS the plain entry point, bit for bit. Any
+ * other kind, or a scale that is not finite and > 0, is CALIB_E_INVALID before any device call.
+ *
+ * calib_rig_robust_normal_eq: the blocks of the weighted problem at Pq; out_cost_cam (N) = sum rho per camera.
+ * calib_rig_robust_step_delta, calib_refine_rig_robust: out_cost = sum rho before the last update, out_cost_cam at the
+ *   returned Pq, trace columns 1 and 2 = sum rho.
+ * calib_rig_residuals: out_res (sum_c n_c, 2) = sensor - projection of every point at Pq, camera 0's n_0 rows first, then
+ *   camera 1's, .., each in the order of its uv; no loss, no mask. */
+#define CALIB_LOSS_NONE 0
+#define CALIB_LOSS_HUBER 1
+#define CALIB_LOSS_CAUCHY 2
+typedef struct {
+    int kind;       /* CALIB_LOSS_* */
+    double scale;   /* d, pixels */
+} calib_loss_t;
+
+int calib_rig_robust_normal_eq(const calib_rig_problem_t* problem, const double* Pq, const calib_loss_t* loss, double* out_B,
+                               double* out_E, double* out_V, double* out_g, double* out_cost_cam, int device_id);
+int calib_rig_robust_step_delta(const calib_rig_problem_t* problem, const double* Pq, const uint64_t* fixed_mask /* [2] */,
+                                const calib_loss_t* loss, double lambda, double* out_delta, int device_id);
+int calib_refine_rig_robust(const calib_rig_problem_t* problem, double* Pq_inout, const uint64_t* fixed_mask /* [2] */,
+                            const calib_loss_t* loss, int max_iters, double lam_init, double lam_min, double lam_max,
+                            double err_min, double* out_cost, double* out_cost_cam, int* out_iters, double* out_trace,
+                            int device_id);
+int calib_rig_residuals(const calib_rig_problem_t* problem, const double* Pq, double* out_res, int device_id);
+
 /* ---- using a calibrated rig: rectify maps, rectified points, triangulation ---------------------------------------
  * Stateless, host pointers, the work runs on device_id; cameras as in the undistortion entries (A (3,3) row-major, k the
  * model's coefficients). R is a (3,3) row-major rotation; |det R - 1| > 1e-6 is CALIB_E_INVALID, as are a bad model id, a
